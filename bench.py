@@ -8,8 +8,11 @@ Lindblad time-steps x initial-conditions per second, whole job.
 
   python bench.py                  one GPU: `value` = BASELINE.json configs[3] on ONE GPU, the largest configuration that fits one
                                    (C4: 3x20 Lindblad, AxC constants, ALL 3600 basis initial conditions, the AxC time grid of 2500
-                                   steps, fp64, forward sweep), validated against the CPU oracle on the sample the CPU baseline
-                                   propagates; plus a compact "workloads" array in the same JSON line (C2, q4 with and without
+                                   steps, fp64, forward sweep).  A plain run sets up, warms up, times the steps and prints the line;
+                                   everything below that takes runs of its own comes with --full.
+  --full                           also: the oracle check of the timed workload on the sample the CPU baseline propagates, the
+                                   CPU baseline, the measured fp64 peak of the roofline, the gradient evaluation of the same
+                                   workload (see --gpus N) and a compact "workloads" array in the same JSON line (C2, q4 with and without
                                    dipole-dipole coupling, C5 fp64 / fp32-mixed, C4 gradient / GMRES / reference Neumann iteration,
                                    the reference's own performance cases nlevels_4_4_4_4 and nlevels_32_32_32_32, one 20x20 state),
                                    each with its roofline fractions and oracle check; `workloads_legend` explains the keys.
@@ -19,16 +22,20 @@ Lindblad time-steps x initial-conditions per second, whole job.
                                    sweep, ntime 2500), STRONG scaling: the initial conditions are split evenly and
                                    contiguously over the GPUs (iinit_global = rank*nlocal + i, src/optimproblem.cpp:248),
                                    the seven objective sums are all-reduced with RCCL (src/optimproblem.cpp:292-298) - so
-                                   value(N) / value(1) of the default lines is the speed-up of one workload.  The same run
-                                   also times the gradient evaluation at the same full size (stored stages beyond HBM are
-                                   handled by propagating and reversing the shard in chunks of initial conditions, one pass;
+                                   value(N) / value(1) of the default lines is the speed-up of one workload.  With --full the
+                                   same run also times the gradient evaluation at the same full size (stored stages beyond HBM
+                                   are handled by propagating and reversing the shard in chunks of initial conditions, one pass;
                                    sums and gradient all-reduced with RCCL, src/optimproblem.cpp:454-460, :527) and reports
-                                   it under "gradient" with its own one-GPU point; `--mode grad` makes it the timed step.
-                                   One GPU: the same gradient evaluation is reported under "gradient" as well.
+                                   it under "gradient" with its own one-GPU point, next to the oracle check of shard 0 and the
+                                   one-GPU point of the timed workload; `--mode grad` makes the gradient the timed step.
+                                   One GPU: --full reports the same gradient evaluation under "gradient" as well.
   --shard-of N                     one GPU: time shard 0 of N of the workload (ninit / N initial conditions) - the strong-scaling
                                    curve minus the two all-reduces, measurable without an N-GPU node.
   --scaling weak                   every GPU propagates one full set of the workload's initial conditions (the
                                    objective is the mean over all replicas and equals the 1-GPU objective).
+  --dump-outputs DIR               after the timed steps: what the last timed step returned to its caller, as DIR/<name>.npy
+                                   (float64): the eight terms of the objective value, and `gradient` when the gradient is timed.
+                                   The inputs are fixed by the workload's seeded configuration: the same arguments, the same inputs.
 
 Prints ONE JSON line on rank 0.
 """
@@ -289,13 +296,23 @@ class Runner:
             self.optim = capi.Optim(self.handle, self.spec, rank=rank, nranks=world)
             self.obj = DistributedObjective(self.optim, comm)
         self.val = None
+        self.grad = None
 
     def one_step(self):
         if self.mode == "fwd":
             self.val = self.obj.evalF(self.spec.params0)
         else:
-            self.val = self.obj.evalGradF(self.spec.params0)[0]
+            self.val, self.grad = self.obj.evalGradF(self.spec.params0)
         return self.val
+
+    def dump_outputs(self, outdir):
+        """What the last step returned to its caller: the objective value's terms and, in grad mode, the gradient (float64)."""
+        os.makedirs(outdir, exist_ok=True)
+        arrays = {k: np.array([v], dtype=np.float64) for k, v in self.val.items()}
+        if self.grad is not None:
+            arrays["gradient"] = np.asarray(self.grad, dtype=np.float64)
+        for k, a in arrays.items():
+            np.save(os.path.join(outdir, k + ".npy"), a)
 
     def time(self, steps, warmup, sync):
         for _ in range(warmup):
@@ -341,7 +358,8 @@ class Runner:
             # adjoint step = ONE more solve of the same size (the transposed one: the primal stage is read back, not re-solved),
             # the gradient contraction (~1 application) and xbar += M^T kbar (1 application, booked with the solve's first one)
             f_step = 2.0 * f_step + f_apply
-        valu_peak = (self.fp32_peak or FP32_PEAK_TFLOPS) if self.dtype == "f32mixed" else fp64_peak
+        # (fp64_peak = 0: no peak measured in this run - a plain run, or a rank other than 0)
+        valu_peak = ((self.fp32_peak or FP32_PEAK_TFLOPS) if fp64_peak > 0.0 else 0.0) if self.dtype == "f32mixed" else fp64_peak
         valu_achieved = f_step * units_per_launch / kern_s / 1e12
         vk = "fp32_valu" if self.dtype == "f32mixed" else "fp64_valu"
         spec_peak = FP32_PEAK_TFLOPS if self.dtype == "f32mixed" else FP64_PEAK_TFLOPS
@@ -351,7 +369,7 @@ class Runner:
         hbm = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                "algorithmic_bytes_per_unit": alg_bytes}
         valu = {"achieved": valu_achieved, "peak": spec_peak, "unit": "TFLOP/s", "frac": valu_achieved / spec_peak,
-                "peak_measured": valu_peak, "frac_of_measured": valu_achieved / valu_peak if valu_peak > 0 else None, "flops_per_unit": f_step,
+                "peak_measured": valu_peak if valu_peak > 0 else None, "frac_of_measured": valu_achieved / valu_peak if valu_peak > 0 else None, "flops_per_unit": f_step,
                 "peak_kind": ("157.3 TFLOP/s = FP32 vector peak (packed), MI355X_MICROARCH.md; peak_measured = v_pk_fma_f32 micro-benchmark on this device (qd_measure_fp32_peak)" if self.dtype == "f32mixed" else
                               "78.6 TFLOP/s = AMD's FP64 vector spec; peak_measured = v_fma_f64 micro-benchmark on this device (qd_measure_fp64_peak)"),
                 "active_cu_frac": min(1.0, ninit_local / 256.0)}
@@ -504,6 +522,12 @@ def main():
     ap.add_argument("--shard-of", type=int, default=0, metavar="N",
                     help="one GPU: time shard 0 of N (ninit / N initial conditions) next to the whole batch: predicted_speedup = T(1) / T(N), "
                          "the strong-scaling curve minus the two all-reduces")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: oracle check, CPU baseline, measured fp64 peak, the gradient evaluation of the same "
+                         "workload, the workloads array (one GPU) / the one-GPU point of the series (several GPUs); the --no-* options "
+                         "below leave parts out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (objective terms, gradient in grad mode) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gradient", action="store_true", help="one GPU: skip the gradient evaluation of the same workload (reported under \"gradient\")")
     ap.add_argument("--no-workloads", action="store_true", help="one GPU: skip the additional workloads array")
@@ -535,12 +559,15 @@ def main():
     multi = world > 1
     name = args.workload or "c4"
     # Default on ANY number of GPUs: the forward sweep of BASELINE config 4 at its full size - one series, so that value(N) / value(1) is
-    # the strong-scaling speed-up of one workload.  On several GPUs the gradient evaluation (forward + adjoint + the RCCL all-reduce of
-    # sums and gradient) is timed in the same run as well and reported under "gradient", with its own one-GPU point.
+    # the strong-scaling speed-up of one workload.  On several GPUs and with --full, the gradient evaluation (forward + adjoint + the RCCL
+    # all-reduce of sums and gradient) is timed in the same run as well and reported under "gradient", with its own one-GPU point.
     mode = args.mode or "fwd"
-    also_grad = multi and args.mode is None
+    full = args.full
+    also_grad = multi and args.mode is None and full
     steps = args.steps if args.steps is not None else (3 if multi else 5)
     warmup = args.warmup if args.warmup is not None else 1
+    if steps < 1 or warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {steps}, {warmup})")
 
     import torch
 
@@ -609,7 +636,9 @@ def main():
     if comm is not None:
         red = comm.allreduce_max(np.array([elapsed, kern_ms] + ar_ms, dtype=np.float64))
         elapsed, kern_ms, ar_ms = float(red[0]), float(red[1]), [float(red[2]), float(red[3])]
-    fp64_peak = capi.measure_fp64_peak(local_rank) if rank == 0 else 0.0
+    if rank == 0 and args.dump_outputs:
+        run.dump_outputs(args.dump_outputs)
+    fp64_peak = capi.measure_fp64_peak(local_rank) if rank == 0 and full else 0.0
     value, roof, cfg = run.report(elapsed, kern_ms, mean_applies, steps, fp64_peak)
 
     out = None
@@ -705,7 +734,7 @@ def main():
             sh["error"] = f"{type(e).__name__}: {e}"
         out["shard"] = sh
 
-    if rank == 0 and not multi and mode == "fwd" and not args.shard_of and not args.no_gradient:
+    if rank == 0 and not multi and full and mode == "fwd" and not args.shard_of and not args.no_gradient:
         # ---- BASELINE.json's metric names the gradient wall time: the gradient evaluation of the SAME workload at the SAME full size
         # (C4: 3600 initial conditions x 2500 steps).  Its stored stages (3600 x 2500 x 57.6 KB = 518 GB) exceed HBM - the storage problem of
         # src/timestepper.cpp:38-48 - so the shard is propagated and reversed in chunks of initial conditions, in one pass (qd_optim.cpp:
@@ -731,7 +760,7 @@ def main():
         except (Exception, SystemExit) as e:  # noqa: BLE001
             out["gradient"] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    if rank == 0 and not multi:
+    if rank == 0 and not multi and full:
         # ---- oracle check of the timed workload + CPU baseline on the same sample -------------------------------
         if not args.no_cpu_baseline:
             block, smp = cpu_baseline(run.spec, mode)
@@ -765,7 +794,7 @@ def main():
                     out["gpu_over_cpu"] = same[0]["v"] / out["cpu_baseline"]["value"]
                     out["gpu_over_cpu_note"] = ("gpu_over_cpu: GPU and CPU both on the reference's Neumann iteration (workloads entry c4 fwd neumann_split=0); "
                                                 "gpu_over_cpu_mixed_iterations: the headline's diagonal-split iteration against the CPU's reference iteration")
-    if rank == 0 and multi:
+    if rank == 0 and multi and full:
         # ---- oracle check of the multi-GPU line: shard 0 of the timed workload on a small sample against the CPU oracle (rank 0 alone, after the
         # timed region; the other ranks wait in the closing barrier) - the solver path and the kernels that were timed
         try:
@@ -777,7 +806,7 @@ def main():
                                    "max_err_rel_to_max1": err, "tol": CHECK_TOL[args.dtype]}
         except (Exception, SystemExit) as e:  # noqa: BLE001
             out["oracle_check"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0 and multi and not weak:
+    if rank == 0 and multi and full and not weak:
         # The same workload on ONE GPU (rank 0 alone, after the timed region): the one-GPU point of this strong-scaling series in
         # the same line.
         ref = {"note": "rank 0 alone on the whole batch, same run, outside the timed region"}

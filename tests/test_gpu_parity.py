@@ -1619,7 +1619,7 @@ def test_bench_two_ranks_matches_one_rank():
 
     outdir = os.path.join(ROOT, "gpurun_out")
     os.makedirs(outdir, exist_ok=True)
-    common = ["--workload", "c2", "--mode", "grad", "--steps", "2", "--warmup", "1", "--ntime", "200", "--no-workloads", "--no-cpu-baseline"]
+    common = ["--workload", "c2", "--mode", "grad", "--steps", "2", "--warmup", "1", "--ntime", "200", "--full", "--no-workloads", "--no-cpu-baseline"]
     res = {}
     for n in (1, 2):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + common, capture_output=True, text=True, timeout=600)
@@ -1635,15 +1635,54 @@ def test_bench_two_ranks_matches_one_rank():
     # before the first sweep, and the multi-rank line validates itself against the CPU oracle (shard 0 on a small sample)
     assert "qd_comm_create_from_file" in res[2]["dist_backend"] and res[2]["allreduce_self_check"].endswith("ok")
     assert res[2]["oracle_check"]["max_err_rel_to_max1"] <= res[2]["oracle_check"]["tol"]
-    # the default invocation: the forward sweep is the timed step on any number of GPUs (one series), the gradient evaluation is
-    # timed in the same run and reported next to it with its own one-GPU point
+    # the default invocation with --full: the forward sweep is the timed step on any number of GPUs (one series), the gradient
+    # evaluation is timed in the same run and reported next to it with its own one-GPU point
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c2", "--steps", "2", "--warmup", "1",
-                        "--ntime", "200", "--no-workloads", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--ntime", "200", "--full", "--no-workloads", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert d["config"]["mode"].startswith("forward sweep") and d["n_gpus"] == 2
     assert d["gradient"]["mode"].startswith("forward + adjoint") and d["gradient"]["value"] > 0.0
     assert d["gradient"]["same_workload_one_gpu"]["speedup"] > 0.0 and d["same_workload_one_gpu"]["speedup"] > 0.0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and prints the headline fields only (the oracle check, CPU baseline, gradient
+    block and workloads array come with --full); --dump-outputs writes what the last timed step returned - the objective terms, and the
+    gradient in grad mode - and the same arguments give the same outputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from helpers import ROOT
+
+    def bench(*args):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--ntime", "50",
+                            "--steps", "3", "--warmup", "1"] + list(args), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    d = bench("--dump-outputs", str(tmp_path / "a"))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0.0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["metric"] == "lindblad_timesteps_x_initconds_per_sec" and d["unit"] == "timesteps*initconds/s" and d["value"] > 0.0
+    assert not {"oracle_check", "cpu_baseline", "gradient", "workloads"} & set(d)
+    a = load(tmp_path / "a")
+    assert set(a) == set(OBJ_KEYS) and all(v.dtype == np.float64 and v.shape == (1,) for v in a.values())
+    assert a["objective"][0] == d["config"]["objective"]
+    bench("--dump-outputs", str(tmp_path / "b"))
+    b = load(tmp_path / "b")
+    for k in OBJ_KEYS:
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-12, atol=1e-15, err_msg=k)
+    g = bench("--mode", "grad", "--dump-outputs", str(tmp_path / "g"))
+    out = load(tmp_path / "g")
+    assert out["objective"][0] == g["config"]["objective"] and out["gradient"].dtype == np.float64 and out["gradient"].size > 0
+    # the headline's oracle check, with --full, on the same workload
+    f = bench("--full", "--no-workloads", "--no-cpu-baseline", "--no-gradient")
+    assert f["oracle_check"]["max_err_rel_to_max1"] <= f["oracle_check"]["tol"]
 
 
 @pytest.mark.parametrize("workload,extra", [("c2", []), ("c3", []), ("c4", ["--set", "initialcondition=basis, 0", "--ntime", "40"])])
