@@ -64,7 +64,7 @@ __global__ void k_big_table(const DevSys S, double2* __restrict__ coef, uint2* _
 template <int Q, bool LIND, bool DENSE = false, bool ADJ = false>
 struct BigTeam {
   // one slot, table-driven (non-hoisted) formulation; DENSE: user-supplied Hamiltonians, G(t) read from the table in global memory
-  typedef typename std::conditional<DENSE, DenseStencil<Q, LIND, 1, 2>, GenStencil<Q, LIND, 1, 2>>::type ST;
+  typedef typename std::conditional<DENSE, DenseStencil<Q, LIND, 1, false>, GenStencil<Q, LIND, 1, false>>::type ST;
   // neighbour reads in batches (GenStencil::apply_batched) wherever the batch has the registers (the Neumann / GMRES kernels are separate
   // instantiations for that reason): everywhere but the Schroedinger adjoint sweep, measured on one lease each - 20 x 20 Lindblad forward
   // 8.9 -> 7.8 ms, gradient 25.0 -> 23.2; 32^4 Schroedinger with six coupling pairs forward 8.2 -> 7.3 ms, but gradient 20.9 -> 23.5

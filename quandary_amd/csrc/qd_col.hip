@@ -1404,34 +1404,26 @@ static hipError_t go_fwd_col_s(const SweepArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
   return hipGetLastError();
 }
-// the Krylov kernels (SweepArgs::use_gmres): five or eight columns per wave only
+// the Krylov kernels (SweepArgs::use_gmres)
 template <int Q, int EPT>
 static hipError_t go_fwd_col_k(const SweepArgs& a, hipStream_t st) {
-  if constexpr (EPT == 5 || EPT == 8) {
-    typedef ColLean<Q, EPT> ST;
-    const size_t lds = ST::lds_bytes(a.S.N) + ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N);
-    auto kf = col_uslot<EPT>(a.S) ? k_forward_col<Q, EPT, true, true, false, true> : k_forward_col<Q, EPT, true, false, false, true>;
-    hipError_t e = set_lds_col(kf, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
+  typedef ColLean<Q, EPT> ST;
+  const size_t lds = ST::lds_bytes(a.S.N) + ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N);
+  auto kf = col_uslot<EPT>(a.S) ? k_forward_col<Q, EPT, true, true, false, true> : k_forward_col<Q, EPT, true, false, false, true>;
+  hipError_t e = set_lds_col(kf, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
+  return hipGetLastError();
 }
 template <int Q, int EPT>
 static hipError_t go_adj_col_k(const SweepArgs& a, hipStream_t st) {
-  if constexpr (EPT == 5 || EPT == 8) {
-    typedef ColLean<Q, EPT> ST;
-    const size_t lds = ST::lds_bytes(a.S.N) + ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N);
-    auto kf = col_uslot<EPT>(a.S) ? k_adjoint_col<Q, EPT, true, true, false, true> : k_adjoint_col<Q, EPT, true, false, false, true>;
-    hipError_t e = set_lds_col(kf, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
-    return hipGetLastError();
-  } else {
-    return hipErrorInvalidValue;
-  }
+  typedef ColLean<Q, EPT> ST;
+  const size_t lds = ST::lds_bytes(a.S.N) + ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N);
+  auto kf = col_uslot<EPT>(a.S) ? k_adjoint_col<Q, EPT, true, true, false, true> : k_adjoint_col<Q, EPT, true, false, false, true>;
+  hipError_t e = set_lds_col(kf, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
+  return hipGetLastError();
 }
 template <int Q, int EPT>
 static hipError_t go_fwd_col(const SweepArgs& a, hipStream_t st) {
@@ -1472,44 +1464,20 @@ static hipError_t go_app_col(const DevSys& S, const double* ctlrow, int tr, cons
 // Columns per wave.  Measured on the 3 x 20 workload (3600 initial conditions x 100 steps, forward sweep, one lease): 4 columns
 // (15 waves, 128 VGPRs, 63 spills) 58.9 ms, 5 columns (12 waves, 168 VGPRs) 48.4 ms, 6 columns (10 waves, 59 spills) 62.9 ms,
 // 8 columns (8 waves, 234 VGPRs, no spills) 53.4 ms; the general column kernel of qd_device.h 73.1 ms.  Five columns per wave cover
-// N <= 60, eight the rest.  The option col_ept overrides (measurements).
-static int col_ept(int N, const TuneOpts& o) {
-  const int f = o.col_ept;
-  if (f == 4 || f == 6 || f == 8 || (f == 5 && N <= 60)) return f;
-  return N <= 60 ? 5 : 8;
-}
-#define QD_COL_DISPATCH(FN, ...)                                  \
-  do {                                                            \
-    const int e = col_ept(Nn, o);                                      \
-    if (Qn == 2) {                                                \
-      if (e == 4) return FN<2, 4>(__VA_ARGS__);                   \
-      if (e == 5 && Nn <= 60) return FN<2, 5>(__VA_ARGS__);       \
-      if (e == 6) return FN<2, 6>(__VA_ARGS__);                   \
-      return FN<2, 8>(__VA_ARGS__);                               \
-    }                                                             \
-    if (Qn == 3) {                                                \
-      if (e == 4) return FN<3, 4>(__VA_ARGS__);                   \
-      if (e == 5 && Nn <= 60) return FN<3, 5>(__VA_ARGS__);       \
-      if (e == 6) return FN<3, 6>(__VA_ARGS__);                   \
-      return FN<3, 8>(__VA_ARGS__);                               \
-    }                                                             \
-    return hipErrorInvalidValue;                                  \
+// N <= 60, eight the rest; only these two are built.
+#define QD_COL_DISPATCH(FN, ...)                                                    \
+  do {                                                                              \
+    if (Qn == 2) return Nn <= 60 ? FN<2, 5>(__VA_ARGS__) : FN<2, 8>(__VA_ARGS__); \
+    if (Qn == 3) return Nn <= 60 ? FN<3, 5>(__VA_ARGS__) : FN<3, 8>(__VA_ARGS__); \
+    return hipErrorInvalidValue;                                                    \
   } while (0)
 
-// (the Krylov kernels are built with five and eight columns per wave: the automatic choices)
-static TuneOpts col_opts(const SweepArgs& a, const TuneOpts& o) {
-  TuneOpts t = o;
-  if (a.use_gmres && t.col_ept != 5 && t.col_ept != 8) t.col_ept = 0;
-  return t;
-}
-hipError_t launch_forward_col(const SweepArgs& a, const TuneOpts& o0, hipStream_t st) {
+hipError_t launch_forward_col(const SweepArgs& a, hipStream_t st) {
   const int Qn = a.S.Q, Nn = a.S.N;
-  const TuneOpts o = col_opts(a, o0);
   QD_COL_DISPATCH(go_fwd_col, a, st);
 }
-hipError_t launch_adjoint_col(const SweepArgs& a, const TuneOpts& o0, hipStream_t st) {
+hipError_t launch_adjoint_col(const SweepArgs& a, hipStream_t st) {
   const int Qn = a.S.Q, Nn = a.S.N;
-  const TuneOpts o = col_opts(a, o0);
   QD_COL_DISPATCH(go_adj_col, a, st);
 }
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st) {

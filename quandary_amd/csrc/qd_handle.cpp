@@ -541,7 +541,7 @@ extern "C" int qd_apply_rhs(qd_handle* h, double t, int transpose, const double*
     QD_HIP(launch_gmat(h->S, h->d_g0.p, h->d_onerow.p, h->cs, 1, h->d_gone.p, h->stream));
     Sone.gtab = h->d_gone.p;
   }
-  if (h->precision == QD_PRECISION_F32MIXED) QD_HIP(launch_apply_f32(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, 1, 0, h->opts, h->stream));
+  if (h->precision == QD_PRECISION_F32MIXED) QD_HIP(launch_apply_f32(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, 1, 0, h->stream));
   else if (cfg.var != 16 && lean64_available(h->S, h->opts)) QD_HIP(launch_apply_lean64(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->stream));
   else if (cfg.var == 9 && collean_available(h->S, h->opts)) QD_HIP(launch_apply_col(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->opts, h->stream));
   else QD_HIP(launch_apply(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, cfg, h->stream));
@@ -985,7 +985,7 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   else if (lean64) QD_HIP(launch_forward_lean64(a, opts, stream));
   else if (use_col(cfg)) {
     if ((r = arm_slices(a, nb, 0))) return r;
-    QD_HIP(launch_forward_col(a, opts, stream));
+    QD_HIP(launch_forward_col(a, stream));
   } else QD_HIP(launch_forward(a, cfg, stream));
   QD_HIP(hipEventRecord(ev1, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(h_sched.p, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
@@ -1217,7 +1217,7 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   else if (lean64) QD_HIP(launch_adjoint_lean64(a, opts, stream));
   else if (use_col(cfg)) {
     if ((r = arm_slices(a, nb, 1))) return r;
-    QD_HIP(launch_adjoint_col(a, opts, stream));
+    QD_HIP(launch_adjoint_col(a, stream));
   } else QD_HIP(launch_adjoint(a, cfg, stream));
   QD_HIP(hipEventRecord(ev3, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
@@ -1296,9 +1296,9 @@ extern "C" int qd_bench_apply_f32(qd_handle* h, double t, const double* x, doubl
   QD_HIP(hipMemcpyAsync(h->d_onetime.p, tt, sizeof tt, hipMemcpyHostToDevice, h->stream));
   QD_HIP(launch_controls(h->dctl, h->d_params.p, h->d_onetime.p, h->d_onetime.p + 1, 1, h->d_onerow.p, h->cs, h->stream));
   QD_HIP(hipMemcpyAsync(h->d_x0.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  QD_HIP(launch_apply_f32(S, h->d_onerow.p, 0, h->d_x0.p, h->d_y.p, nb, nrep, mfma, h->opts, h->stream));  // warm-up
+  QD_HIP(launch_apply_f32(S, h->d_onerow.p, 0, h->d_x0.p, h->d_y.p, nb, nrep, mfma, h->stream));  // warm-up
   QD_HIP(hipEventRecord(h->ev0, h->stream));
-  QD_HIP(launch_apply_f32(S, h->d_onerow.p, 0, h->d_x0.p, h->d_y.p, nb, nrep, mfma, h->opts, h->stream));
+  QD_HIP(launch_apply_f32(S, h->d_onerow.p, 0, h->d_x0.p, h->d_y.p, nb, nrep, mfma, h->stream));
   QD_HIP(hipEventRecord(h->ev1, h->stream));
   QD_HIP(hipMemcpyAsync(y, h->d_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   QD_HIP(hipStreamSynchronize(h->stream));

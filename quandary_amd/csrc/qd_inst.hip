@@ -20,31 +20,6 @@ namespace qd {
 constexpr bool kQubit = (QD_B == 1);
 constexpr bool kDense = (QD_B == 2);  // user-supplied dense Hamiltonians (DenseStencil)
 constexpr bool kLind = (QD_L != 0);
-// all-qubit systems have a fixed dimension, so only the matching variants are built
-constexpr int kQubitDim = kLind ? (1 << (2 * QD_Q)) : (1 << QD_Q);
-
-template <int VAR>
-constexpr bool variant_built() {
-  // Built = what pick_config() can select.  Measured on MI355X and therefore NOT built: V6/V7 (two initial
-  // conditions interleaved per workgroup: higher per-wave throughput, but the batches of this problem
-  // class never exceed the number of SIMDs, so one initial condition per wave wins, C2 38.6M vs 26.7M
-  // units/s); V3 and V5 (1024-thread blocks: 128 VGPRs are not enough, 8-12x slower than V2 on C5); V8 and
-  // V10 (column layout with 4 / 6 columns per wave: 4.0M vs 4.85M units/s of V9 on C4).
-  // ... and only where the variant's size class is reachable with this many oscillators (every oscillator has at
-  // least two levels: dim >= 2^Q, or 4^Q for Lindblad) - the five-oscillator Lindblad unit alone took 6 minutes
-  constexpr long kMinDim = kLind ? (1L << (2 * QD_Q)) : (1L << QD_Q);
-  constexpr bool fits0 = kMinDim <= 64, fits1 = kMinDim <= 256, fits2 = kMinDim <= 1024;
-  // six to eight oscillators, Lindblad (beyond the reference's matrix-free templates, mastereq.cpp:2977-3239): the eight-elements-per-thread
-  // LDS kernel for 2^6 (dim 4096, the only such system that fits a CU) and the global-memory kernels
-  if (kLind && QD_Q >= 6 && !kDense) return (VAR == 4 && QD_Q == 6) || VAR == 16;
-  if (kDense && QD_Q >= 6) return VAR == 16 || (!kLind && ((VAR == 11 && fits0) || (VAR == 12 && fits1) || (VAR == 13 && fits2)));
-  if (kDense) return (VAR == 11 && fits0) || (VAR == 12 && fits1) || (VAR == 13 && fits2) || (kLind && VAR == 15 && QD_Q <= 4) || (kLind && VAR == 17 && QD_Q <= 5) || VAR == 16;
-  if (!kQubit) return (VAR == 0 && fits0) || (VAR == 1 && fits1) || (VAR == 2 && fits2) || VAR == 4 || (kLind && (VAR == 9 || VAR == 14)) || VAR == 16;
-  if (kQubitDim <= 64) return VAR == 0;
-  if (kQubitDim <= 256) return VAR == 1;
-  return VAR == 2;
-}
-
 template <typename K>
 static hipError_t set_lds(K kern, size_t bytes) {
   if (bytes > 48 * 1024)
@@ -70,16 +45,16 @@ static hipError_t set_lds(K kern, size_t bytes) {
 #if QD_PART == 0 || QD_PART == 2
 template <int VAR>
 static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && variant_built<VAR>()) {
+  if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     return launch_big(reinterpret_cast<const void*>(k_forward_big<QD_Q, kLind, kDense, kGmPart>), a, cfg, st);
-  } else if constexpr (VAR != 16 && variant_built<VAR>()) {
+  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart>;
     if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
       if (plain_sweep(a, cfg, 0)) kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
     }
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kf, dim3((a.nb + Variant<VAR>::ICPB - 1) / Variant<VAR>::ICPB), dim3(cfg.block), cfg.lds, st, a);
+    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
   } else {
     return hipErrorInvalidValue;
@@ -90,16 +65,16 @@ static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream
 template <int VAR>
 static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb,
                            const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && variant_built<VAR>()) {
+  if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     DevSys S1 = S;  // one operator application: no exchange between workgroups after the load, no team needed
     S1.team = 1;
     hipLaunchKernelGGL((k_apply_big<QD_Q, kLind, kDense>), dim3(nb), dim3(cfg.block), cfg.lds, st, S1, ctlrow, transpose, x, y, nb);
     return hipGetLastError();
-  } else if constexpr (variant_built<VAR>()) {
+  } else if constexpr (variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_apply<QD_Q, kLind, VAR, kQubit>;
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kf, dim3((nb + Variant<VAR>::ICPB - 1) / Variant<VAR>::ICPB), dim3(cfg.block), cfg.lds, st, S, ctlrow, transpose, x, y, nb);
+    hipLaunchKernelGGL(kf, dim3(nb), dim3(cfg.block), cfg.lds, st, S, ctlrow, transpose, x, y, nb);
     return hipGetLastError();
   } else {
     return hipErrorInvalidValue;
@@ -110,19 +85,19 @@ static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose,
 #if QD_PART == 1 || QD_PART == 3
 template <int VAR>
 static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && variant_built<VAR>()) {
+  if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     if constexpr (!kGmPart) {
       if (a.stepper_ee) return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, false, true>), a, cfg, st);
     }
     return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, kGmPart, false>), a, cfg, st);
-  } else if constexpr (VAR != 16 && variant_built<VAR>()) {
+  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart>;
     if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
       if (plain_sweep(a, cfg, 1)) kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
     }
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kf, dim3((a.nb + Variant<VAR>::ICPB - 1) / Variant<VAR>::ICPB), dim3(cfg.block), cfg.lds, st, a);
+    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
   } else {
     return hipErrorInvalidValue;
@@ -135,14 +110,8 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     case 0: return FN<0>(__VA_ARGS__);       \
     case 1: return FN<1>(__VA_ARGS__);       \
     case 2: return FN<2>(__VA_ARGS__);       \
-    case 3: return FN<3>(__VA_ARGS__);       \
     case 4: return FN<4>(__VA_ARGS__);       \
-    case 5: return FN<5>(__VA_ARGS__);       \
-    case 6: return FN<6>(__VA_ARGS__);       \
-    case 7: return FN<7>(__VA_ARGS__);       \
-    case 8: return FN<8>(__VA_ARGS__);       \
     case 9: return FN<9>(__VA_ARGS__);       \
-    case 10: return FN<10>(__VA_ARGS__);     \
     case 11: return FN<11>(__VA_ARGS__);     \
     case 12: return FN<12>(__VA_ARGS__);     \
     case 13: return FN<13>(__VA_ARGS__);     \

@@ -146,13 +146,11 @@ struct TuneOpts {
   int big_team = 0;        // "big_team": workgroups per initial condition of the global-memory sweeps (0 = automatic)
   int big_spread = -1;     // "big_spread": team members dealt over all XCDs (1), kept on one (0), default (-1)
   int big_blocked = 2;     // "big_blocked": a team member owns a contiguous block of the state (1; 2: the members of an XCD own neighbouring blocks) or every 'team'th row of 1024 elements (0)
-  int f32_sb = -1;         // "f32_sb": slot bits of the fp32-mixed 2^4 kernel
   int lean64_sb = 0;       // "lean64_sb": elements per thread of the fp64 2^5 kernels as a power of two (0 = automatic: 2 elements on 512 threads for batches of
                            // at most one state per CU, else 4 on 256; 1 / 2 force)
   int no_lean64 = 0;       // "no_lean64": 2^5 / 2^4 Lindblad on the general slot kernels
   int no_collean = 0;      // "no_collean": 3 x 20-class systems on the general column kernel
   int no_col_krylov = 0;   // "no_col_krylov": the Krylov solver of 3 x 20-class systems on the general column kernel (A/B against the lean one [r6])
-  int col_ept = 0;         // "col_ept": columns per wave of the lean column kernels (0 = automatic)
   double standin_tau = 1e-3;  // "standin_tau": error-estimate factor of the stationary iterations that serve gmres requests (0 = plain update-norm rule)
   int krylov_restart = 14;    // "krylov_restart": restart length of the generic path of the lean column kernels' Krylov solver (1 .. 14; KSPGMRESSetRestart)
   double krylov_tau = 0.1;    // "krylov_tau": the one-vector path of the Krylov solvers accepts at residual <= krylov_tau x the reference's tolerance (1 = at the tolerance itself)
@@ -217,7 +215,7 @@ hipError_t launch_grad(const DevCtlDesc& d, const double* params, const double* 
 hipError_t launch_forward_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
 hipError_t launch_adjoint_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
-                            const TuneOpts& o, hipStream_t st);
+                            hipStream_t st);
 // the same lean slot kernel instantiated in fp64: Neumann sweeps of the 2^5 Lindblad system (QD_PRECISION_F64)
 bool lean64_available(const DevSys& S, const TuneOpts& o);
 hipError_t launch_forward_lean64(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
@@ -227,8 +225,8 @@ hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transp
 bool collean_available(const DevSys& S, const TuneOpts& o);
 int col_slices(int nb, int ntime, const TuneOpts& o);  // time slices of a lean column sweep (1 = none)
 size_t col_krylov_doubles(int nb, int nslice);  // size of SweepArgs::kry for the Krylov solver of the lean column kernels
-hipError_t launch_forward_col(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
-hipError_t launch_adjoint_col(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
+hipError_t launch_forward_col(const SweepArgs& a, hipStream_t st);
+hipError_t launch_adjoint_col(const SweepArgs& a, hipStream_t st);
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false, bool adjoint = false);
 size_t krylov_doubles(const DevSys& S, int nb);

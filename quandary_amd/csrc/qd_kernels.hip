@@ -428,19 +428,18 @@ __global__ void k_gmat(const DevSys S, const double* __restrict__ g0, const doub
 // regime): more elements per thread so that several workgroups share a CU.
 constexpr int QD_COL_DEFAULT = 9;
 
-// host-side view of the kernel variants, generated from the Variant<> traits of qd_device.h
+// host-side view of the kernel variants, generated from the Variant<> traits of qd_device.h (zero for the removed numbers)
 struct VarInfo {
-  int ept, icpb, maxb;
+  int ept, maxb;
   bool dbuf, col;
 };
 template <int V>
 constexpr VarInfo var_info() {
-  return {Variant<V>::EPT, Variant<V>::ICPB, Variant<V>::MAXB, Variant<V>::DBUF, Variant<V>::COL};
+  return {Variant<V>::EPT, Variant<V>::MAXB, Variant<V>::DBUF, Variant<V>::COL};
 }
-static const VarInfo kVar[NVARIANTS] = {var_info<0>(), var_info<1>(), var_info<2>(),  var_info<3>(),  var_info<4>(),
-                                        var_info<5>(), var_info<6>(), var_info<7>(),  var_info<8>(),  var_info<9>(),
-                                        var_info<10>(), var_info<11>(), var_info<12>(), var_info<13>(), var_info<14>(),
-                                        var_info<15>(), var_info<16>(), var_info<17>()};
+static const VarInfo kVar[NVARIANTS] = {var_info<0>(), var_info<1>(),  var_info<2>(),  {},             var_info<4>(),  {},
+                                        {},            {},             {},             var_info<9>(),  {},             var_info<11>(),
+                                        var_info<12>(), var_info<13>(), var_info<14>(), var_info<15>(), var_info<16>(), var_info<17>()};
 int variant_max_block(int var) { return (var >= 0 && var < NVARIANTS) ? kVar[var].maxb : 0; }
 
 void big_team(const DevSys& S, int nb, const TuneOpts& o, int& team, int& spread);
@@ -454,7 +453,7 @@ LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmre
   c.qubit = S.dense ? 2 : qubit ? 1 : 0;
   c.noplain = o.no_plain;
   const bool gm = want_gmres && !o.force_neumann;
-  // column layout (V8/V9): one wave per column of rho, N <= 64 lanes used
+  // column layout (V9): one wave per column of rho, N <= 64 lanes used
   // V14 packs floor(64 / N) columns into one wave slot
   auto colblock = [&](int v) {
     const int cpw = (v == 14 && S.N <= 64) ? 64 / S.N : 1, slots = (S.N + cpw - 1) / cpw;
@@ -462,14 +461,8 @@ LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmre
   };
   auto fits = [&](int v) {
     if (v == 14 && S.N > 32) return false;
-    if (kVar[v].col) return S.lindblad && !qubit && S.N <= 64 && colblock(v) <= kVar[v].maxb && lds_bytes(S, colblock(v), true, false, 2, 1, true) <= 160 * 1024;
-    return (dim + (kVar[v].ept / kVar[v].icpb) - 1) / (kVar[v].ept / kVar[v].icpb) <= kVar[v].maxb;
-  };
-  auto built = [&](int v) {  // mirrors variant_built() in qd_inst.hip
-    if (S.dense) return (v >= 11 && v <= 13) || (v == 15 && S.lindblad && S.N == 16) || (v == 17 && S.lindblad && S.N > 16 && S.N <= 32);
-    if (S.lindblad && S.Q > 5) return v == 4 && S.Q == 6;
-    if (!qubit) return v <= 2 || v == 4 || (S.lindblad && (v == 9 || v == 14));
-    return dim <= 64 ? v == 0 : dim <= 256 ? v == 1 : v == 2;
+    if (kVar[v].col) return S.lindblad && !qubit && S.N <= 64 && colblock(v) <= kVar[v].maxb && lds_bytes(S, colblock(v), true, false, 2, true) <= 160 * 1024;
+    return (dim + kVar[v].ept - 1) / kVar[v].ept <= kVar[v].maxb;
   };
   int var;
   if (dim <= 64) var = 0;
@@ -488,7 +481,10 @@ LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmre
   if (S.dense && S.lindblad && S.N >= 22 && S.N <= 32 && !o.no_mfma) var = 17;
   if (o.var >= 0) {  // tuning override
     const int v = o.var;
-    if (v >= 0 && v < NVARIANTS && built(v) && fits(v)) var = v;
+    // (the matrix-core kernels are written for one density-matrix size: V15 N = 16, V17 16 < N <= 32)
+    if (v >= 0 && v < NVARIANTS && variant_built(S.Q, S.lindblad, c.qubit, v) && fits(v) && (v != 15 || S.N == 16) &&
+        (v != 17 || (S.N > 16 && S.N <= 32)))
+      var = v;
   }
   // beyond one CU's LDS: work vectors in global memory (qd_big.h); general stencil whatever the level structure.
   // the option var = 16 forces it onto small systems (parity tests of this path against everything the LDS kernels are tested on)
@@ -502,21 +498,20 @@ LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmre
     c.blocked = o.big_blocked;
     return c;
   }
-  const int epe = kVar[var].ept / kVar[var].icpb;
   c.var = var;
-  c.block = kVar[var].col ? colblock(var) : ((dim + epe - 1) / epe + 63) / 64 * 64;
+  c.block = kVar[var].col ? colblock(var) : ((dim + kVar[var].ept - 1) / kVar[var].ept + 63) / 64 * 64;
   if (var == 17) c.block = 256;  // four waves = the four 16 x 16 tiles, whatever N
   c.gmres = 0;
   const bool dn = S.dense == 2;  // G(t) staged in LDS
-  c.lds = lds_bytes(S, c.block, kVar[var].dbuf, false, 0, kVar[var].icpb, kVar[var].col, dn);
-  if (gm && kVar[var].icpb == 1) {
-    const size_t in_lds = lds_bytes(S, c.block, kVar[var].dbuf, false, 1, kVar[var].icpb, kVar[var].col, dn);
+  c.lds = lds_bytes(S, c.block, kVar[var].dbuf, false, 0, kVar[var].col, dn);
+  if (gm) {
+    const size_t in_lds = lds_bytes(S, c.block, kVar[var].dbuf, false, 1, kVar[var].col, dn);
     if (kVar[var].ept == 1 && in_lds <= 160 * 1024) {  // Krylov basis in LDS
       c.gmres = 1;
       c.lds = in_lds;
     } else {  // Krylov basis in global memory
       c.gmres = 2;
-      c.lds = lds_bytes(S, c.block, kVar[var].dbuf, false, 2, kVar[var].icpb, kVar[var].col, dn);
+      c.lds = lds_bytes(S, c.block, kVar[var].dbuf, false, 2, kVar[var].col, dn);
     }
   }
   return c;
@@ -560,8 +555,8 @@ size_t krylov_doubles(const DevSys& S, int nb) { return (size_t)nb * (GMRES_MR_G
 // ---------------------------------------------------------------------------------------------
 // options
 // ---------------------------------------------------------------------------------------------
-static const char* const kOptKeys[] = {"var", "force_neumann", "no_mfma", "big_team", "big_spread", "big_blocked", "f32_sb", "lean64_sb", "no_lean64", "no_collean",
-                                       "col_ept", "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
+static const char* const kOptKeys[] = {"var", "force_neumann", "no_mfma", "big_team", "big_spread", "big_blocked", "lean64_sb", "no_lean64", "no_collean",
+                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
 int TuneOpts::set(const char* key, const char* value) {
   if (!key || !value) return -1;
   const std::string k(key), v(value);
@@ -591,7 +586,7 @@ int TuneOpts::set(const char* key, const char* value) {
     return 0;
   }
   long iv;
-  if (v == "auto") iv = (k == "var" || k == "big_spread" || k == "f32_sb" || k == "neumann_split" || k == "gmres_split") ? -1 : 0;
+  if (v == "auto") iv = (k == "var" || k == "big_spread" || k == "neumann_split" || k == "gmres_split") ? -1 : 0;
   else {
     iv = strtol(value, &end, 10);
     if (end == value) return -1;
@@ -602,14 +597,12 @@ int TuneOpts::set(const char* key, const char* value) {
   else if (k == "big_team") big_team = (int)iv;
   else if (k == "big_spread") big_spread = (int)iv;
   else if (k == "big_blocked") big_blocked = v == "auto" ? 2 : (int)(iv < 0 ? 0 : iv > 2 ? 2 : iv);
-  else if (k == "f32_sb") f32_sb = (int)iv;
   else if (k == "lean64_sb") lean64_sb = (iv == 1 || iv == 2) ? (int)iv : 0;
   else if (k == "no_lean64") no_lean64 = iv != 0;
   else if (k == "col_skip") col_skip = v == "auto" ? 1 : iv != 0;
   else if (k == "no_collean") no_collean = iv != 0;
   else if (k == "no_col_krylov") no_col_krylov = iv != 0;
   else if (k == "krylov_restart") krylov_restart = (v == "auto" || iv < 1 || iv > 14) ? 14 : (int)iv;
-  else if (k == "col_ept") col_ept = (int)iv;
   else if (k == "no_plain") no_plain = (int)(iv & 3);
   else if (k == "col_slices") col_slices = iv > 0 ? (int)iv : 0;
   else if (k == "col_min_n") col_min_n = iv > 0 ? (int)iv : 33;

@@ -1496,13 +1496,6 @@ static hipError_t set_lds32(K kern, size_t bytes) {
   return hipSuccess;
 }
 
-// slot bits per thread for a Q-qubit Lindblad system: 2^5 -> 4 elements per thread (256 threads); 2^4 -> one element per
-// thread (256 threads; the option f32_sb = 2 selects the one-wave, four-elements-per-thread layout for measurements)
-static int q32_slot_bits(int Q, const TuneOpts& o) {
-  if (Q == 5) return 2;
-  return o.f32_sb == 2 ? 2 : 0;
-}
-
 template <int Q, int SB, typename R, bool GM = false, bool HJ = false>
 static hipError_t go_fwd(const SweepArgs& a, hipStream_t st) {
   constexpr int nt = Q32<Q, SB, R>::NT;
@@ -1541,7 +1534,6 @@ static bool small_batch_sb1(const SweepArgs& a, const TuneOpts& o) {
 }
 
 hipError_t launch_forward_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st) {
-  const int sb = q32_slot_bits(a.S.Q, o);
   if (a.S.hasJ) {  // [r6] dipole-dipole coupling: the coupled stencils in fp32 (stationary iterations only)
     if (a.use_gmres) return hipErrorInvalidValue;
     if (a.S.Q == 5) return go_fwd<5, 1, float, false, true>(a, st);
@@ -1555,12 +1547,11 @@ hipError_t launch_forward_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t
     return hipErrorInvalidValue;
   }
   if (a.S.Q == 5) return small_batch_sb1(a, o) ? go_fwd<5, 1, float>(a, st) : go_fwd<5, 2, float>(a, st);
-  if (a.S.Q == 4) return sb == 2 ? go_fwd<4, 2, float>(a, st) : go_fwd<4, 0, float>(a, st);
+  if (a.S.Q == 4) return go_fwd<4, 0, float>(a, st);
   if (a.S.Q == 3) return go_fwd<3, 0, float>(a, st);  // [r3] 2x2x2 (BASELINE config 2): one wave per initial condition
   return hipErrorInvalidValue;
 }
 hipError_t launch_adjoint_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st) {
-  const int sb = q32_slot_bits(a.S.Q, o);
   if (a.S.hasJ) {
     if (a.use_gmres) return hipErrorInvalidValue;
     if (a.S.Q == 5) return go_adj<5, 1, float, false, true>(a, st);
@@ -1574,25 +1565,24 @@ hipError_t launch_adjoint_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t
     return hipErrorInvalidValue;
   }
   if (a.S.Q == 5) return small_batch_sb1(a, o) ? go_adj<5, 1, float>(a, st) : go_adj<5, 2, float>(a, st);
-  if (a.S.Q == 4) return sb == 2 ? go_adj<4, 2, float>(a, st) : go_adj<4, 0, float>(a, st);
+  if (a.S.Q == 4) return go_adj<4, 0, float>(a, st);
   if (a.S.Q == 3) return go_adj<3, 0, float>(a, st);
   return hipErrorInvalidValue;
 }
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
-                            const TuneOpts& o, hipStream_t st) {
+                            hipStream_t st) {
   if (mfma) {
     if (S.Q != 5 || transpose) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_apply_mfma32, dim3(nb), dim3(64), 0, st, S, ctlrow, x, y, nrep);
     return hipGetLastError();
   }
-  const int sb = q32_slot_bits(S.Q, o);
   if (S.hasJ) {
     if (S.Q == 5) return go_app<5, 1, float, true>(S, ctlrow, transpose, x, y, nb, nrep, st);
     if (S.Q == 4) return go_app<4, 0, float, true>(S, ctlrow, transpose, x, y, nb, nrep, st);
     return hipErrorInvalidValue;
   }
   if (S.Q == 5) return go_app<5, 2, float>(S, ctlrow, transpose, x, y, nb, nrep, st);
-  if (S.Q == 4) return sb == 2 ? go_app<4, 2, float>(S, ctlrow, transpose, x, y, nb, nrep, st) : go_app<4, 0, float>(S, ctlrow, transpose, x, y, nb, nrep, st);
+  if (S.Q == 4) return go_app<4, 0, float>(S, ctlrow, transpose, x, y, nb, nrep, st);
   if (S.Q == 3) return go_app<3, 0, float>(S, ctlrow, transpose, x, y, nb, nrep, st);
   return hipErrorInvalidValue;
 }
