@@ -174,7 +174,7 @@ EXPORTS = [
     "qd_last_error", "qd_version", "qd_device_count", "qd_create", "qd_destroy", "qd_dim", "qd_dim_rho",
     "qd_dim_ess", "qd_ndesign", "qd_set_hamiltonian", "qd_set_params", "qd_eval_controls", "qd_apply_rhs", "qd_get_state",
     "qd_set_target", "qd_set_penalty", "qd_forward", "qd_adjoint", "qd_last_mean_applies",
-    "qd_last_forward_ms", "qd_last_adjoint_ms", "qd_last_team", "qd_last_solver", "qd_measure_fp64_peak", "qd_measure_fp32_peak", "qd_optim_create", "qd_optim_destroy", "qd_optim_ninit",
+    "qd_last_forward_ms", "qd_last_adjoint_ms", "qd_last_team", "qd_last_solver", "qd_last_kernel", "qd_measure_fp64_peak", "qd_measure_fp32_peak", "qd_optim_create", "qd_optim_destroy", "qd_optim_ninit",
     "qd_optim_ninit_local", "qd_optim_initial_state", "qd_optim_target_state", "qd_optim_forward_local",
     "qd_optim_finalize", "qd_optim_adjoint_local", "qd_optim_gradient_local", "qd_optim_evalF", "qd_optim_evalGradF",
     "qd_comm_unique_id", "qd_comm_create", "qd_comm_create_from_file", "qd_comm_create_host", "qd_comm_backend", "qd_comm_destroy", "qd_comm_size", "qd_comm_rank",
@@ -228,6 +228,8 @@ def load_library(path=None):
         getattr(lib, f).restype = C.c_double
     lib.qd_last_team.argtypes = [vp]
     lib.qd_last_solver.argtypes = [vp]
+    lib.qd_last_kernel.argtypes = [vp, C.c_int]
+    lib.qd_last_kernel.restype = C.c_char_p
     lib.qd_measure_fp64_peak.argtypes = [C.c_int, C.POINTER(C.c_double)]
     lib.qd_measure_fp32_peak.argtypes = [C.c_int, C.POINTER(C.c_double)]
     lib.qd_optim_create.argtypes = [vp, C.POINTER(qd_objective), C.c_int, C.c_int, C.POINTER(vp)]
@@ -444,6 +446,14 @@ class Handle:
         """Which iteration solved the linear systems of the last sweep (qd_last_solver): 'neumann', 'krylov' (the in-kernel GMRES),
         'gmres_as_split' / 'gmres_as_neumann' (a gmres request served by a stationary iteration), 'none' (explicit Euler)."""
         return self.SOLVER_NAMES[self.lib.qd_last_solver(self._h)]
+
+    KERNEL_ROLES = {"forward": 0, "adjoint": 1, "apply": 2}
+
+    def last_kernel(self, which):
+        """Test hook (qd_last_kernel): the kernel instantiation last launched for `which` - 0 / 'forward', 1 / 'adjoint', 2 / 'apply' -
+        as `nm -C` spells it, e.g. 'k_forward_col<3, 8, true, false, false, false>'; '' before the first launch."""
+        which = self.KERNEL_ROLES.get(which, which)
+        return self.lib.qd_last_kernel(self._h, int(which)).decode()
 
     @property
     def forward_ms(self):

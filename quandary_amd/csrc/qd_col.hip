@@ -1396,11 +1396,12 @@ static hipError_t go_fwd_col_s(const SweepArgs& a, hipStream_t st) {
   // (SKIP: stopping tests skipped, see ColTeam::stage)
   // (implicit midpoint only: the predictor compares the pass count of a sub-step with its predecessor's, and the sub-steps of a composite
   //  step differ in size - IMR4 / IMR8 test every pass; nothing of this lives in the kernels)
-  const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;
-  auto kf = col_uslot<EPT>(a.S) ? (skip ? k_forward_col<Q, EPT, SPLIT, true, true> : k_forward_col<Q, EPT, SPLIT, true, false>)
-                                : (skip ? k_forward_col<Q, EPT, SPLIT, false, true> : k_forward_col<Q, EPT, SPLIT, false, false>);
+  const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1, uslot = col_uslot<EPT>(a.S);
+  auto kf = uslot ? (skip ? k_forward_col<Q, EPT, SPLIT, true, true> : k_forward_col<Q, EPT, SPLIT, true, false>)
+                  : (skip ? k_forward_col<Q, EPT, SPLIT, false, true> : k_forward_col<Q, EPT, SPLIT, false, false>);
   hipError_t e = set_lds_col(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(0, "k_forward_col", Q, EPT, SPLIT, uslot, skip, false);
   hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
   return hipGetLastError();
 }
@@ -1409,9 +1410,11 @@ template <int Q, int EPT>
 static hipError_t go_fwd_col_k(const SweepArgs& a, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
   const size_t lds = ST::lds_bytes(a.S.N) + ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N);
-  auto kf = col_uslot<EPT>(a.S) ? k_forward_col<Q, EPT, true, true, false, true> : k_forward_col<Q, EPT, true, false, false, true>;
+  const bool uslot = col_uslot<EPT>(a.S);
+  auto kf = uslot ? k_forward_col<Q, EPT, true, true, false, true> : k_forward_col<Q, EPT, true, false, false, true>;
   hipError_t e = set_lds_col(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(0, "k_forward_col", Q, EPT, true, uslot, false, true);
   hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
   return hipGetLastError();
 }
@@ -1419,9 +1422,11 @@ template <int Q, int EPT>
 static hipError_t go_adj_col_k(const SweepArgs& a, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
   const size_t lds = ST::lds_bytes(a.S.N) + ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N);
-  auto kf = col_uslot<EPT>(a.S) ? k_adjoint_col<Q, EPT, true, true, false, true> : k_adjoint_col<Q, EPT, true, false, false, true>;
+  const bool uslot = col_uslot<EPT>(a.S);
+  auto kf = uslot ? k_adjoint_col<Q, EPT, true, true, false, true> : k_adjoint_col<Q, EPT, true, false, false, true>;
   hipError_t e = set_lds_col(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(1, "k_adjoint_col", Q, EPT, true, uslot, false, true);
   hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
   return hipGetLastError();
 }
@@ -1436,11 +1441,12 @@ static hipError_t go_adj_col_s(const SweepArgs& a, hipStream_t st) {
   const size_t lds = ST::lds_bytes(a.S.N);
   // (implicit midpoint only: the predictor compares the pass count of a sub-step with its predecessor's, and the sub-steps of a composite
   //  step differ in size - IMR4 / IMR8 test every pass; nothing of this lives in the kernels)
-  const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;
-  auto kf = col_uslot<EPT>(a.S) ? (skip ? k_adjoint_col<Q, EPT, SPLIT, true, true> : k_adjoint_col<Q, EPT, SPLIT, true, false>)
-                                : (skip ? k_adjoint_col<Q, EPT, SPLIT, false, true> : k_adjoint_col<Q, EPT, SPLIT, false, false>);
+  const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1, uslot = col_uslot<EPT>(a.S);
+  auto kf = uslot ? (skip ? k_adjoint_col<Q, EPT, SPLIT, true, true> : k_adjoint_col<Q, EPT, SPLIT, true, false>)
+                  : (skip ? k_adjoint_col<Q, EPT, SPLIT, false, true> : k_adjoint_col<Q, EPT, SPLIT, false, false>);
   hipError_t e = set_lds_col(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(1, "k_adjoint_col", Q, EPT, SPLIT, uslot, skip, false);
   hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, 64 * (ST::ncols(a.S.N) / EPT), lds)), dim3(64 * (ST::ncols(a.S.N) / EPT)), lds, st, a);
   return hipGetLastError();
 }
@@ -1457,6 +1463,7 @@ static hipError_t go_app_col(const DevSys& S, const double* ctlrow, int tr, cons
   auto kf = split ? k_apply_col<Q, EPT, true> : k_apply_col<Q, EPT, false>;
   hipError_t e = set_lds_col(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(2, "k_apply_col", Q, EPT, split);
   hipLaunchKernelGGL(kf, dim3(nb), dim3(64 * (ST::ncols(S.N) / EPT)), lds, st, S, ctlrow, tr, x, y);
   return hipGetLastError();
 }

@@ -11,6 +11,13 @@
 namespace qd {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+static thread_local std::string g_kernel[3];
+std::string& kernel_record(int role) { return g_kernel[role]; }
+std::string take_kernel(int role) {
+  std::string s;
+  s.swap(g_kernel[role]);
+  return s;
+}
 }  // namespace qd
 
 using namespace qd;
@@ -541,10 +548,12 @@ extern "C" int qd_apply_rhs(qd_handle* h, double t, int transpose, const double*
     QD_HIP(launch_gmat(h->S, h->d_g0.p, h->d_onerow.p, h->cs, 1, h->d_gone.p, h->stream));
     Sone.gtab = h->d_gone.p;
   }
+  take_kernel(2);
   if (h->precision == QD_PRECISION_F32MIXED) QD_HIP(launch_apply_f32(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, 1, 0, h->stream));
   else if (cfg.var != 16 && lean64_available(h->S, h->opts)) QD_HIP(launch_apply_lean64(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->stream));
   else if (cfg.var == 9 && collean_available(h->S, h->opts)) QD_HIP(launch_apply_col(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->opts, h->stream));
   else QD_HIP(launch_apply(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, cfg, h->stream));
+  h->last_kernel[2] = take_kernel(2);
   QD_HIP(hipMemcpyAsync(y, h->d_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   QD_HIP(hipStreamSynchronize(h->stream));
   return QD_OK;
@@ -694,7 +703,9 @@ void qd_handle::row_bounds(double* diag, double* off) const {
 // sub-step, from the system constants and the CURRENT control parameters (|p_k(t)|, |q_k(t)| <= sum over carriers of
 // max |alpha^1| + max |alpha^2|: the quadratic B-splines are a partition of unity, src/controlbasis.cpp:81-96; pi-pulses
 // by their amplitude).  The option gmres_poly overrides the degree (1 = never precondition).
-int qd_handle::gmres_poly_degree() const {
+// lean_col: the sweep runs on the Krylov solver of the lean column kernels (use_col with cfg.gmres), whose polynomial is that of the
+// diagonal-split iteration; every other solver gets the plain Neumann polynomial and the full-row gate.
+int qd_handle::gmres_poly_degree(bool lean_col) const {
   const int want = opts.gmres_poly > 0 ? opts.gmres_poly : poly_cur;  // tuned in forward_finish
   // only where the Krylov basis traffic is the cost (dim > 1024: the column / eight-elements-per-thread kernels); below
   // that plain GMRES keeps the oracle's iteration path, and with it results that agree far below the solver tolerance
@@ -707,16 +718,18 @@ int qd_handle::gmres_poly_degree() const {
   double amax = 0.0;
   for (double hh : sched_h) amax = std::max(amax, fabs(hh) / 2.0);
   // the lean column kernels precondition with the polynomial of the diagonal-split iteration [r6]: only the off-diagonal row sum has
-  // to contract (ColTeam::kry_*, qd_col.hip)
-  if (precision == QD_PRECISION_F64 && collean_available(S, opts) && S.N >= 44) return amax * of <= 0.7 ? want : 1;
+  // to contract (ColTeam::kry_*, qd_col.hip).  The general column kernel's GMRES (Team::gmres_g) - option no_col_krylov, a forced
+  // variant - applies sum (alpha M)^i, which needs the whole row: at dt = 0.05 on 3 x 20 (alpha |D| ~ 5) it runs un-preconditioned.
+  if (lean_col && S.N >= 44) return amax * of <= 0.7 ? want : 1;
   return amax * (dg + of) <= 0.7 ? want : 1;
 }
 
-// the lean column kernels: the stationary iterations, and [r6] the Krylov solver wherever the polynomial preconditioner is on (without
-// it - KSPGMRES + PCNONE iteration for iteration - a gmres request stays on the general column kernel)
+// the lean column kernels: the stationary iterations, and [r6] the Krylov solver wherever its polynomial preconditioner is on - under
+// the off-diagonal gate of gmres_poly_degree(true).  Without it (KSPGMRES + PCNONE iteration for iteration) or with the option
+// no_col_krylov a gmres request stays on the general column kernel, preconditioned only where the full-row gate holds.
 bool qd_handle::use_col(const qd::LaunchCfg& cfg) const {
   if (!(precision == QD_PRECISION_F64 && cfg.var == 9 && collean_available(S, opts) && sol.stepper != QD_STEPPER_EE)) return false;
-  return !cfg.gmres || (cfg.gmres == 2 && !opts.no_col_krylov && gmres_poly_degree() > 1);
+  return !cfg.gmres || (cfg.gmres == 2 && !opts.no_col_krylov && gmres_poly_degree(true) > 1);
 }
 
 // linearsolver_type = gmres on the systems of the lean column kernels.  A Krylov basis of 57.6 KB vectors per initial condition has no
@@ -848,7 +861,7 @@ static void fill_sweep(const qd_handle* h, SweepArgs& a, int nb, const DevTarget
   a.reltol = h->sol.reltol;
   a.inv_abs2 = 1.0 / (a.abstol * a.abstol);
   a.rel2 = (float)(a.reltol * a.reltol);
-  a.gmres_poly = h->gmres_poly_degree();
+  a.gmres_poly = 1;  // (set by the launch once its kernel family is known: gmres_poly_degree)
   a.col_noskip = !h->opts.col_skip;
   a.kry_tau2 = h->opts.krylov_tau * h->opts.krylov_tau;
   a.kry_restart = h->opts.krylov_restart;
@@ -933,8 +946,6 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   if ((r = ensure_wj_weights())) return r;
   SweepArgs a;
   fill_sweep(this, a, nb, tgp);
-  last_poly = a.gmres_poly;
-  fwd_poly = a.gmres_poly;
   a.x0 = dx0;
   a.xT = d_xT.p;
   a.traj = full ? d_traj.p : nullptr;
@@ -944,6 +955,9 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   a.napply = d_napply;
   LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES);
   last_var = cfg.var;
+  a.gmres_poly = gmres_poly_degree(use_col(cfg) && cfg.gmres);
+  last_poly = a.gmres_poly;
+  fwd_poly = a.gmres_poly;
   last_team = cfg.var == 16 && cfg.team > 1 && precision != QD_PRECISION_F32MIXED ? cfg.team : 1;
   a.use_gmres = cfg.gmres;
   last_solver = sol.stepper == QD_STEPPER_EE ? QD_SOLVER_NONE : cfg.gmres ? QD_SOLVER_KRYLOV : QD_SOLVER_NEUMANN;
@@ -981,12 +995,14 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   if (a.ztraj) ztraj_fmt = precision == QD_PRECISION_F32MIXED ? 1 : lean64 ? 2 : use_col(cfg) ? 3 : 0;
   if (precision == QD_PRECISION_F32MIXED && S.hasJ && a.use_gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
+  take_kernel(0);
   if (precision == QD_PRECISION_F32MIXED) QD_HIP(launch_forward_f32(a, opts, stream));
   else if (lean64) QD_HIP(launch_forward_lean64(a, opts, stream));
   else if (use_col(cfg)) {
     if ((r = arm_slices(a, nb, 0))) return r;
     QD_HIP(launch_forward_col(a, stream));
   } else QD_HIP(launch_forward(a, cfg, stream));
+  last_kernel[0] = take_kernel(0);
   QD_HIP(hipEventRecord(ev1, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(h_sched.p, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_fwd = a.sched != nullptr;
@@ -1165,9 +1181,6 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   if ((r = ensure_wj_weights())) return r;
   SweepArgs a;
   fill_sweep(this, a, nb, tgp);
-  // (the adjoint sweep of an evaluation runs on the degree its forward sweep ran on: the tuner moves between the two, forward_finish)
-  if (opts.gmres_poly == 0 && fwd_poly > 1 && a.gmres_poly > 1) a.gmres_poly = fwd_poly;
-  last_poly = a.gmres_poly;
   const bool have_states = pending_store ? pending_full : traj_full;
   if (!have_states && adjoint_reads_states(nb, tgp))
     return fail(QD_ERR_STATE, "qd_adjoint: the forward sweep stored the primal stages only, this adjoint sweep needs the states");
@@ -1177,6 +1190,10 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   a.jbar = djbar;
   a.coeff = d_coeff.p;
   LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES, /*adjoint=*/true);
+  a.gmres_poly = gmres_poly_degree(use_col(cfg) && cfg.gmres);
+  // (the adjoint sweep of an evaluation runs on the degree its forward sweep ran on: the tuner moves between the two, forward_finish)
+  if (opts.gmres_poly == 0 && fwd_poly > 1 && a.gmres_poly > 1) a.gmres_poly = fwd_poly;
+  last_poly = a.gmres_poly;
   last_team = cfg.var == 16 && cfg.team > 1 && precision != QD_PRECISION_F32MIXED ? cfg.team : 1;
   a.use_gmres = cfg.gmres;
   last_solver = sol.stepper == QD_STEPPER_EE ? QD_SOLVER_NONE : cfg.gmres ? QD_SOLVER_KRYLOV : QD_SOLVER_NEUMANN;
@@ -1213,12 +1230,14 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
     return fail(QD_ERR_STATE, "qd_adjoint: the primal stages were stored by another kernel family (options or precision changed since the forward sweep): repeat the forward sweep");
   if (precision == QD_PRECISION_F32MIXED && S.hasJ && a.use_gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0)");
+  take_kernel(1);
   if (precision == QD_PRECISION_F32MIXED) QD_HIP(launch_adjoint_f32(a, opts, stream));
   else if (lean64) QD_HIP(launch_adjoint_lean64(a, opts, stream));
   else if (use_col(cfg)) {
     if ((r = arm_slices(a, nb, 1))) return r;
     QD_HIP(launch_adjoint_col(a, stream));
   } else QD_HIP(launch_adjoint(a, cfg, stream));
+  last_kernel[1] = take_kernel(1);
   QD_HIP(hipEventRecord(ev3, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_adj = a.sched != nullptr;
@@ -1278,6 +1297,7 @@ extern "C" double qd_last_forward_ms(const qd_handle* h) { return h ? h->last_fw
 extern "C" double qd_last_adjoint_ms(const qd_handle* h) { return h ? h->last_adj_ms : 0.0; }
 extern "C" int qd_last_team(const qd_handle* h) { return h ? h->last_team : QD_ERR_INVALID; }
 extern "C" int qd_last_solver(const qd_handle* h) { return h ? h->last_solver : QD_ERR_INVALID; }
+extern "C" const char* qd_last_kernel(const qd_handle* h, int which) { return h && which >= 0 && which < 3 ? h->last_kernel[which].c_str() : ""; }
 
 // Measurement hook ("settle the MFMA question"): nrep chained applications of the forward operator
 // to nb copies... of a batch of states with the fp32 stencil kernel (mfma = 0) or with the dense Kronecker-factor
@@ -1298,7 +1318,9 @@ extern "C" int qd_bench_apply_f32(qd_handle* h, double t, const double* x, doubl
   QD_HIP(hipMemcpyAsync(h->d_x0.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
   QD_HIP(launch_apply_f32(S, h->d_onerow.p, 0, h->d_x0.p, h->d_y.p, nb, nrep, mfma, h->stream));  // warm-up
   QD_HIP(hipEventRecord(h->ev0, h->stream));
+  take_kernel(2);
   QD_HIP(launch_apply_f32(S, h->d_onerow.p, 0, h->d_x0.p, h->d_y.p, nb, nrep, mfma, h->stream));
+  h->last_kernel[2] = take_kernel(2);
   QD_HIP(hipEventRecord(h->ev1, h->stream));
   QD_HIP(hipMemcpyAsync(y, h->d_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   QD_HIP(hipStreamSynchronize(h->stream));

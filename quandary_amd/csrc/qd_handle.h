@@ -106,6 +106,7 @@ struct qd_handle {
   int ndesign = 0, dim_ess = 1;
   int last_team = 1;  // workgroups per initial condition of the last sweep (qd_big.h)
   int last_solver = 0;  // QD_SOLVER_* of the last sweep (qd_last_solver)
+  std::string last_kernel[3];  // instantiation last launched per role: forward, adjoint, apply (qd_last_kernel)
   bool has_pipulse = false;
   bool has_ampbasis = false;  // a spline_amplitude segment: forward only (src/oscillator.cpp:350-356)
   std::vector<double> params;
@@ -155,7 +156,7 @@ struct qd_handle {
   mutable double hmax_cache = -1.0;  // max |h(I)| over the level combinations (system constant, computed on first use)
   double control_amplitude_bound(int k) const;       // max_t |p_k(t)|, |q_k(t)| for the current parameters
   void row_bounds(double* diag, double* off) const;  // Gershgorin bounds of a row of M over all sub-steps (current parameters)
-  int gmres_poly_degree() const;  // > 1 where the Neumann series provably contracts for the current parameters, else 1
+  int gmres_poly_degree(bool lean_col) const;  // > 1 where the Neumann series provably contracts for the current parameters, else 1
   // degree of the polynomial preconditioner, tuned from sweep to sweep (forward_finish): smallest degree with one Krylov vector per solve
   int poly_cur = 6, poly_lo = 1, poly_hi = 0, last_poly = 1, last_var = 0, poly_steps = 0;
   int fwd_poly = 0;  // degree the last forward sweep ran on (the adjoint sweep of the same evaluation keeps it)

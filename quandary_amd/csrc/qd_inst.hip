@@ -46,14 +46,18 @@ static hipError_t set_lds(K kern, size_t bytes) {
 template <int VAR>
 static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
+    note_kernel(0, "k_forward_big", QD_Q, kLind, kDense, kGmPart);
     return launch_big(reinterpret_cast<const void*>(k_forward_big<QD_Q, kLind, kDense, kGmPart>), a, cfg, st);
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart>;
+    bool plain = false;
     if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      if (plain_sweep(a, cfg, 0)) kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+      plain = plain_sweep(a, cfg, 0);
+      if (plain) kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
     }
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
+    note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
   } else {
@@ -68,12 +72,14 @@ static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose,
   if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     DevSys S1 = S;  // one operator application: no exchange between workgroups after the load, no team needed
     S1.team = 1;
+    note_kernel(2, "k_apply_big", QD_Q, kLind, kDense);
     hipLaunchKernelGGL((k_apply_big<QD_Q, kLind, kDense>), dim3(nb), dim3(cfg.block), cfg.lds, st, S1, ctlrow, transpose, x, y, nb);
     return hipGetLastError();
   } else if constexpr (variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_apply<QD_Q, kLind, VAR, kQubit>;
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
+    note_kernel(2, "k_apply", QD_Q, kLind, VAR, kQubit);
     hipLaunchKernelGGL(kf, dim3(nb), dim3(cfg.block), cfg.lds, st, S, ctlrow, transpose, x, y, nb);
     return hipGetLastError();
   } else {
@@ -87,16 +93,23 @@ template <int VAR>
 static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     if constexpr (!kGmPart) {
-      if (a.stepper_ee) return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, false, true>), a, cfg, st);
+      if (a.stepper_ee) {
+        note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, false, true);
+        return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, false, true>), a, cfg, st);
+      }
     }
+    note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, kGmPart, false);
     return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, kGmPart, false>), a, cfg, st);
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart>;
+    bool plain = false;
     if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      if (plain_sweep(a, cfg, 1)) kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+      plain = plain_sweep(a, cfg, 1);
+      if (plain) kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
     }
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
+    note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
   } else {

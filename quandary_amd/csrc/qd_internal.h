@@ -236,4 +236,23 @@ int variant_max_block(int var);  // 0 for an unknown variant  // size of SweepAr
 
 void set_error(const std::string& msg);
 
+// The kernel instantiation a launcher started last, per role (0 forward sweep, 1 adjoint sweep, 2 operator application), spelled as
+// `nm -C` prints it: note_kernel(0, "k_forward_col", Q, EPT, SPLIT, ...) -> "k_forward_col<3, 8, true, false, false, false>".
+// Host side only, per calling thread; the handle takes the record after each launch (qd_last_kernel).
+inline void kernel_arg(std::string& s, bool v) { s += v ? "true" : "false"; }
+inline void kernel_arg(std::string& s, int v) { s += std::to_string(v); }
+inline void kernel_arg(std::string& s, const char* v) { s += v; }  // a type argument: "float" / "double"
+std::string& kernel_record(int role);
+template <typename... A>
+void note_kernel(int role, const char* base, A... args) {
+  std::string& s = kernel_record(role);
+  s = base;
+  if constexpr (sizeof...(A) > 0) {
+    const char* sep = "<";
+    ((s += sep, kernel_arg(s, args), sep = ", "), ...);
+    s += ">";
+  }
+}
+std::string take_kernel(int role);  // the record, cleared
+
 }  // namespace qd

@@ -1496,6 +1496,9 @@ static hipError_t set_lds32(K kern, size_t bytes) {
   return hipSuccess;
 }
 
+template <typename R>
+static const char* type_name() { return sizeof(R) == 4 ? "float" : "double"; }  // (note_kernel)
+
 template <int Q, int SB, typename R, bool GM = false, bool HJ = false>
 static hipError_t go_fwd(const SweepArgs& a, hipStream_t st) {
   constexpr int nt = Q32<Q, SB, R>::NT;
@@ -1503,6 +1506,7 @@ static hipError_t go_fwd(const SweepArgs& a, hipStream_t st) {
   auto kf = k_forward_q32<Q, SB, R, GM, HJ>;
   hipError_t e = set_lds32(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(0, "k_forward_q32", Q, SB, type_name<R>(), GM, HJ);
   hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
   return hipGetLastError();
 }
@@ -1513,6 +1517,7 @@ static hipError_t go_adj(const SweepArgs& a, hipStream_t st) {
   auto kf = k_adjoint_q32<Q, SB, R, GM, HJ>;
   hipError_t e = set_lds32(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(1, "k_adjoint_q32", Q, SB, type_name<R>(), GM, HJ);
   hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
   return hipGetLastError();
 }
@@ -1523,6 +1528,7 @@ static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const do
   auto kf = k_apply_q32<Q, SB, R, HJ>;
   hipError_t e = set_lds32(kf, lds);
   if (e != hipSuccess) return e;
+  note_kernel(2, "k_apply_q32", Q, SB, type_name<R>(), HJ);
   hipLaunchKernelGGL(kf, dim3(nb), dim3(nt), lds, st, S, ctlrow, tr, x, y, nrep);
   return hipGetLastError();
 }
@@ -1573,6 +1579,7 @@ hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose
                             hipStream_t st) {
   if (mfma) {
     if (S.Q != 5 || transpose) return hipErrorInvalidValue;
+    note_kernel(2, "k_apply_mfma32");
     hipLaunchKernelGGL(k_apply_mfma32, dim3(nb), dim3(64), 0, st, S, ctlrow, x, y, nrep);
     return hipGetLastError();
   }

@@ -154,3 +154,23 @@ def check_parity(sp, val, g, oval, og, alpha=None, obj_abs=1e-12, grad_abs=1e-13
         assert np.linalg.norm(g - tg) <= 1.25 * np.linalg.norm(og - tg) + 1e-12, msg
         assert np.linalg.norm(g - og) <= 1e-8 * np.linalg.norm(og) + 5e-10, msg
     return "stopping-error"
+
+
+# ---- which kernel instantiation a sweep runs on (qd_last_kernel) -------------------------------------------------------------------------
+def _b(v):
+    return "true" if v else "false"
+
+
+def col_kernels(nlevels, split="0", stepper="IMR", krylov=False):
+    """The lean column kernels (qd_col.hip) a Lindblad system of 33 <= N <= 64 rows runs on, as qd_last_kernel names them, per role.
+    The dispatch rule of QD_COL_DISPATCH / col_uslot / go_*_col: five columns per wave up to N = 60, eight above; USLOT where N and the
+    strides of all oscillators but the last are multiples of it; SPLIT from the option neumann_split ("auto" is on for these ladders; the
+    operator application takes SPLIT only from neumann_split = 1); SKIP on the one-stage implicit midpoint rule with reltol = 0 (the
+    synthetic systems: 1e-20); the Krylov kernels (gmres_split = 0) are always SPLIT and never SKIP."""
+    N, Q = int(np.prod(nlevels)), len(nlevels)
+    ept = 5 if N <= 60 else 8
+    post = [int(np.prod(nlevels[k + 1:])) for k in range(Q)]
+    uslot = N % ept == 0 and all(p % ept == 0 for p in post[:-1])
+    sw_split, skip = (True, False) if krylov else (split != "0", stepper == "IMR")
+    args = f"{Q}, {ept}, {_b(sw_split)}, {_b(uslot)}, {_b(skip)}, {_b(krylov)}"
+    return {"forward": f"k_forward_col<{args}>", "adjoint": f"k_adjoint_col<{args}>", "apply": f"k_apply_col<{Q}, {ept}, {_b(split == '1')}>"}

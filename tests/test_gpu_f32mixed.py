@@ -46,6 +46,7 @@ def test_f32_operator_application(q):
     for tr in (False, True):
         y, yo = h.apply_rhs(t, x, transpose=tr), orc.apply_rhs(t, x, transpose=tr)
         assert np.abs(y - yo).max() <= APPLY_TOL * np.abs(yo).max()
+        assert h.last_kernel("apply") == f"k_apply_q32<{q}, {2 if q == 5 else 0}, float, false>"  # (tests/test_gpu_kernel_coverage.py)
     h.close(); orc.close()
 
 
@@ -59,6 +60,9 @@ def test_f32_objective_and_gradient_budget_ntime1000(q, init, penalties):
     h = capi.Handle(sp)
     opt = capi.Optim(h, sp)
     val, g = opt.evalGradF(sp.params0)
+    # (a few initial conditions: two elements per thread for 2^5; tests/test_gpu_kernel_coverage.py counts these as covered here)
+    args = f"{q}, {1 if q == 5 else 0}, float, false, false"
+    assert (h.last_kernel("forward"), h.last_kernel("adjoint")) == (f"k_forward_q32<{args}>", f"k_adjoint_q32<{args}>")
     val2 = opt.evalF(sp.params0)
     errs = {"objective_rel": abs(val["objective"] - oval["objective"]) / abs(oval["objective"]),
             "fidelity_abs": abs(val["fidelity"] - oval["fidelity"]),
@@ -97,6 +101,9 @@ def test_f32_gmres_objective_and_gradient_budget_ntime1000(q, init, penalties, g
     assert errs["objective_rel"] <= OBJ_RTOL, errs
     assert errs["fidelity_abs"] <= FID_ATOL, errs
     assert errs["gradient_rel_norm"] <= GRAD_TOL, errs
+    if gmres_mode == "0":  # (tests/test_gpu_kernel_coverage.py counts these as covered here)
+        args = f"{q}, {2 if q == 5 else 0}, float, true, false"
+        assert (h.last_kernel("forward"), h.last_kernel("adjoint")) == (f"k_forward_q32<{args}>", f"k_adjoint_q32<{args}>")
     if h.last_solver == "krylov":
         assert h.mean_applies <= orc.mean_applies + 0.5, errs
     else:  # (served by the Neumann iteration: not the optimal polynomial, a few applications more at most)
@@ -122,6 +129,7 @@ def test_f32_coupled_operator_application(q, detuned):
         for tr in (False, True):
             y, yo = h.apply_rhs(t, x, transpose=tr), orc.apply_rhs(t, x, transpose=tr)
             assert np.abs(y - yo).max() <= APPLY_TOL * np.abs(yo).max(), (t, tr)
+            assert h.last_kernel("apply") == f"k_apply_q32<{q}, {1 if q == 5 else 0}, float, true>"  # (tests/test_gpu_kernel_coverage.py)
     h.close(); orc.close()
 
 
@@ -137,6 +145,8 @@ def test_f32_coupled_objective_and_gradient_budget_ntime1000(q, init, penalties,
     h = capi.Handle(sp)
     opt = capi.Optim(h, sp)
     val, g = opt.evalGradF(sp.params0)
+    args = f"{q}, {1 if q == 5 else 0}, float, false, true"  # (tests/test_gpu_kernel_coverage.py counts these as covered here)
+    assert (h.last_kernel("forward"), h.last_kernel("adjoint")) == (f"k_forward_q32<{args}>", f"k_adjoint_q32<{args}>")
     errs = {"objective_rel": abs(val["objective"] - oval["objective"]) / abs(oval["objective"]),
             "fidelity_abs": abs(val["fidelity"] - oval["fidelity"]),
             "gradient_rel_norm": float(np.linalg.norm(g - og) / np.linalg.norm(og)),
@@ -210,6 +220,7 @@ def test_mfma_f32_dense_product_vs_stencil():
     for mfma in (False, True):
         y, _ = h.bench_apply_f32(t, x, nrep=1, mfma=mfma)
         assert np.abs(y - yo).max() <= APPLY_TOL * np.abs(yo).max(), mfma
+        assert h.last_kernel("apply") == ("k_apply_mfma32" if mfma else "k_apply_q32<5, 2, float, false>")  # (tests/test_gpu_kernel_coverage.py)
     xb = rng.standard_normal((1024, 2 * h.dim))
     out = {}
     for mfma in (False, True):

@@ -9,7 +9,7 @@ north-star figure of 1e-8 relative on the gradient norm where noted.
 import numpy as np
 import pytest
 
-from helpers import GMRES_MODES, REF_ATOL, REF_RTOL, SOLVERS, check_parity, golden_grad, golden_history, golden_rows, load_case, synthetic_spec, with_gmres_mode
+from helpers import GMRES_MODES, REF_ATOL, REF_RTOL, SOLVERS, check_parity, col_kernels, golden_grad, golden_history, golden_rows, load_case, synthetic_spec, with_gmres_mode
 from oracle.oracle import Oracle
 from quandary_amd import capi
 
@@ -176,11 +176,14 @@ def test_lean_column_kernels(kw, stepper, split):
     orc.set_params(sp.params0)
     x = rng.standard_normal((3, 2 * h.dim))
     t = 0.41 * sp.time.ntime * sp.time.dt
+    kernels = col_kernels(kw["nlevels"], split, stepper)  # (the instantiations tests/test_gpu_kernel_coverage.py counts as covered here)
     for tr in (False, True):
         yo = orc.apply_rhs(t, x, transpose=tr)
         np.testing.assert_allclose(h.apply_rhs(t, x, transpose=tr), yo, rtol=1e-13, atol=1e-13 * np.abs(yo).max())
+        assert h.last_kernel("apply") == kernels["apply"]
     opt = capi.Optim(h, sp)
     val, g = opt.evalGradF(sp.params0)
+    assert (h.last_kernel("forward"), h.last_kernel("adjoint")) == (kernels["forward"], kernels["adjoint"])
     oval, og = orc.evalGradF(sp.params0)
     for k in OBJ_KEYS:
         assert val[k] == pytest.approx(oval[k], rel=REF_RTOL, abs=1e-12), k
@@ -374,13 +377,17 @@ def test_lean_column_krylov_solver(kw, dt, poly):
     with the polynomial of the diagonal-split iteration.  The fused one-vector path (dt = 1e-4, tuned degree), the generic path behind it
     (degree 3 / 2: several Krylov vectors per solve, basis in global memory) and time steps far outside the contraction region of the
     reference's Neumann series (dt = 0.05: alpha |D| ~ 5) - at the reference tolerances against the oracle, or - where the oracle's GMRES
-    stops at its iteration cap - against the exact solution of the discrete equations."""
+    stops at its iteration cap - against the exact solution of the discrete equations.  Then the general column kernel (option
+    no_col_krylov): the same method up to the preconditioner's form where the plain Neumann polynomial contracts, un-preconditioned -
+    the oracle's iteration - where it does not."""
     sp = synthetic_spec(**{**kw, "ntime": 24, "linsolve": "gmres", "penalties": True, "dt": dt})
     sp.options = {"gmres_split": "0", "gmres_poly": poly}
     h, orc = capi.Handle(sp), Oracle(sp)
     opt = capi.Optim(h, sp)
     val, g = opt.evalGradF(sp.params0)
     assert h.last_solver == "krylov"
+    kernels = col_kernels(kw["nlevels"], krylov=True)  # (tests/test_gpu_kernel_coverage.py counts these as covered here)
+    assert (h.last_kernel("forward"), h.last_kernel("adjoint")) == (kernels["forward"], kernels["adjoint"])
     if dt < 0.05:
         oval, og = orc.evalGradF(sp.params0)
         assert check_parity(sp, val, g, oval, og, msg=(kw, dt, poly)) == "plain"
@@ -397,10 +404,24 @@ def test_lean_column_krylov_solver(kw, dt, poly):
     # the same evaluation on the general column kernel (the lean one switched off): same method up to the preconditioner's form
     h.set_option("no_col_krylov", "1")
     val2, g2 = opt.evalGradF(sp.params0)
-    if dt < 0.05:  # (at dt = 0.05 the Neumann polynomial of the general kernel diverges: it runs un-preconditioned there and stops at the cap)
+    assert h.last_kernel("forward").startswith("k_forward<") and h.last_kernel("adjoint").startswith("k_adjoint<")
+    if dt < 0.05:
         for k in OBJ_KEYS:
             assert val2[k] == pytest.approx(val[k], rel=1e-8, abs=1e-11), k
         assert np.linalg.norm(g2 - g) <= 1e-8 * np.linalg.norm(g) + 1e-12
+    else:
+        # the general kernel (Team::gmres_g) preconditions with the plain Neumann polynomial, which needs the whole row to contract: the
+        # full-row gate of qd_handle::gmres_poly_degree.  3x20 at dt = 0.05 (alpha |D| ~ 5) fails it and runs un-preconditioned - the
+        # evaluation with gmres_poly = 1 forced, to round-off; 3x3x5 and 4x4x4 (alpha ||M|| ~ 0.5 .. 0.6) pass it and may differ from
+        # that evaluation by the solver tolerance only.  Both against the oracle's GMRES with the same iteration cap.
+        h.set_option("gmres_poly", "1")
+        val3, g3 = opt.evalGradF(sp.params0)
+        exact = kw["nlevels"] == [3, 20]
+        for k in OBJ_KEYS:
+            assert val2[k] == (pytest.approx(val3[k], rel=1e-13, abs=1e-13) if exact else pytest.approx(val3[k], rel=1e-8, abs=1e-11)), k
+        assert np.linalg.norm(g2 - g3) <= (1e-13 * np.linalg.norm(g3) if exact else 1e-8 * np.linalg.norm(g3) + 1e-12)
+        oval, og = orc.evalGradF(sp.params0)
+        check_parity(sp, val2, g2, oval, og, msg=(kw, dt, poly, "no_col_krylov"))
     opt.close(); h.close(); orc.close()
 
 
@@ -417,6 +438,8 @@ def test_lean_column_krylov_solver_restarts(kw, restart):
     val, g = opt.evalGradF(sp.params0)
     a_restarted = h.mean_applies
     assert h.last_solver == "krylov"
+    kernels = col_kernels(kw["nlevels"], krylov=True)  # (tests/test_gpu_kernel_coverage.py counts these as covered here)
+    assert (h.last_kernel("forward"), h.last_kernel("adjoint")) == (kernels["forward"], kernels["adjoint"])
     from helpers import tight_oracle
     tight = tight_oracle(sp)
     tval, tg = tight.evalGradF(sp.params0)
