@@ -549,10 +549,12 @@ extern "C" int qd_apply_rhs(qd_handle* h, double t, int transpose, const double*
     Sone.gtab = h->d_gone.p;
   }
   take_kernel(2);
-  if (h->precision == QD_PRECISION_F32MIXED) QD_HIP(launch_apply_f32(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, 1, 0, h->stream));
-  else if (cfg.var != 16 && lean64_available(h->S, h->opts)) QD_HIP(launch_apply_lean64(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->stream));
-  else if (cfg.var == 9 && collean_available(h->S, h->opts)) QD_HIP(launch_apply_col(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->opts, h->stream));
-  else QD_HIP(launch_apply(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, cfg, h->stream));
+  switch (h->apply_family(cfg)) {
+    case Family::F32: QD_HIP(launch_apply_f32(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, 1, 0, h->stream)); break;
+    case Family::Slot: QD_HIP(launch_apply_lean64(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->stream)); break;
+    case Family::Col: QD_HIP(launch_apply_col(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, h->opts, h->stream)); break;
+    default: QD_HIP(launch_apply(Sone, h->d_onerow.p, transpose, h->d_x0.p, h->d_y.p, nb, cfg, h->stream));  // General and Global
+  }
   h->last_kernel[2] = take_kernel(2);
   QD_HIP(hipMemcpyAsync(y, h->d_y.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   QD_HIP(hipStreamSynchronize(h->stream));
@@ -703,33 +705,32 @@ void qd_handle::row_bounds(double* diag, double* off) const {
 // sub-step, from the system constants and the CURRENT control parameters (|p_k(t)|, |q_k(t)| <= sum over carriers of
 // max |alpha^1| + max |alpha^2|: the quadratic B-splines are a partition of unity, src/controlbasis.cpp:81-96; pi-pulses
 // by their amplitude).  The option gmres_poly overrides the degree (1 = never precondition).
-// lean_col: the sweep runs on the Krylov solver of the lean column kernels (use_col with cfg.gmres), whose polynomial is that of the
+// lean_col: the sweep runs on the Krylov solver of the lean column kernels (col_sweep with cfg.gmres), whose polynomial is that of the
 // diagonal-split iteration; every other solver gets the plain Neumann polynomial and the full-row gate.
-int qd_handle::gmres_poly_degree(bool lean_col) const {
+int qd_handle::gmres_poly_degree(bool lean_col, const RowBound& b) const {
   const int want = opts.gmres_poly > 0 ? opts.gmres_poly : poly_cur;  // tuned in forward_finish
   // only where the Krylov basis traffic is the cost (dim > 1024: the column / eight-elements-per-thread kernels); below
   // that plain GMRES keeps the oracle's iteration path, and with it results that agree far below the solver tolerance
   // [r6] ... except on the lean slot kernels (2^4 / 2^5 Lindblad, fp64): their Krylov solver takes the whole solve in ONE preconditioned
   // vector and one reduction (Team32::kry1, qd_q32.hip) - faster than the stationary iteration it is asked instead of
+  // NOTE: slot_kry is not the predicate by which pick_family() selects the slot kernels: that one also asks cfg.var != 16 and an
+  // implicit stepper.  So the option var = 16 on a 2^4 / 2^5 Lindblad system runs the global-memory GMRES with a polynomial that the
+  // dim > 1024 rule would not give it.  Kept as it is (the degree is what the tuner sees); the fix is to pass the plan's family in.
   const bool slot_kry = precision == QD_PRECISION_F64 && lean64_available(S, opts);
   if (want <= 1 || S.dense || (S.dim <= 1024 && !slot_kry)) return 1;
-  double dg, of;
-  row_bounds(&dg, &of);
-  double amax = 0.0;
-  for (double hh : sched_h) amax = std::max(amax, fabs(hh) / 2.0);
   // the lean column kernels precondition with the polynomial of the diagonal-split iteration [r6]: only the off-diagonal row sum has
   // to contract (ColTeam::kry_*, qd_col.hip).  The general column kernel's GMRES (Team::gmres_g) - option no_col_krylov, a forced
   // variant - applies sum (alpha M)^i, which needs the whole row: at dt = 0.05 on 3 x 20 (alpha |D| ~ 5) it runs un-preconditioned.
-  if (lean_col && S.N >= 44) return amax * of <= 0.7 ? want : 1;
-  return amax * (dg + of) <= 0.7 ? want : 1;
+  if (lean_col && S.N >= 44) return b.amax * b.off <= 0.7 ? want : 1;
+  return b.amax * (b.diag + b.off) <= 0.7 ? want : 1;
 }
 
 // the lean column kernels: the stationary iterations, and [r6] the Krylov solver wherever its polynomial preconditioner is on - under
 // the off-diagonal gate of gmres_poly_degree(true).  Without it (KSPGMRES + PCNONE iteration for iteration) or with the option
 // no_col_krylov a gmres request stays on the general column kernel, preconditioned only where the full-row gate holds.
-bool qd_handle::use_col(const qd::LaunchCfg& cfg) const {
+bool qd_handle::col_sweep(const LaunchCfg& cfg, const RowBound& b) const {
   if (!(precision == QD_PRECISION_F64 && cfg.var == 9 && collean_available(S, opts) && sol.stepper != QD_STEPPER_EE)) return false;
-  return !cfg.gmres || (cfg.gmres == 2 && !opts.no_col_krylov && gmres_poly_degree(true) > 1);
+  return !cfg.gmres || (cfg.gmres == 2 && !opts.no_col_krylov && gmres_poly_degree(true, b) > 1);
 }
 
 // linearsolver_type = gmres on the systems of the lean column kernels.  A Krylov basis of 57.6 KB vectors per initial condition has no
@@ -740,19 +741,15 @@ bool qd_handle::use_col(const qd::LaunchCfg& cfg) const {
 // rule: residual <= max(rtol ||b||, abstol) (KSPGMRES defaults as set in src/timestepper.cpp:541-550), checked through the bound
 // ||b - (I - alpha M) y_m|| = ||(1 - alpha D)(y_{m+1} - y_m)|| <= kappa ||y_{m+1} - y_m||.  Same linear system, same tolerance, hence
 // results that agree with GMRES at solver-tolerance level; the option gmres_split = 0 keeps the Krylov kernels.
-bool qd_handle::gmres_as_split(const qd::LaunchCfg& cfg, double* kappa2) const {
+bool qd_handle::gmres_as_split(const LaunchCfg& cfg, const RowBound& b, double* kappa2) const {
   // ... and on the states beyond LDS (qd_big.h), where the Krylov basis streams through HBM (the reference's nlevels_32_32_32_32 case:
   // 12 vectors of 16 MB per initial condition) and the level energies of high levels dominate the row
   const bool col_ok = cfg.var == 9 && collean_available(S, opts), big_ok = cfg.var == 16 && !S.dense;
   if (precision != QD_PRECISION_F64 || !(col_ok || big_ok) || !cfg.gmres || sol.stepper == QD_STEPPER_EE || opts.gmres_split == 0)
     return false;
-  double dg, of;
-  row_bounds(&dg, &of);
-  double amax = 0.0;
-  for (double hh : sched_h) amax = std::max(amax, fabs(hh) / 2.0);
-  if (kappa2) *kappa2 = (1.0 + amax * dg) * (1.0 + amax * dg);
+  *kappa2 = (1.0 + b.amax * b.diag) * (1.0 + b.amax * b.diag);  // (also where the latch then declines: the Krylov kernels do not read it)
   if (opts.gmres_split == 1) return true;
-  return latched_substitution(1, amax * of);
+  return latched_substitution(1, b.amax * b.off);
 }
 
 // The gates depend on the CURRENT control parameters, and an optimiser's line search compares objectives far below the solver
@@ -784,44 +781,93 @@ bool qd_handle::latched_substitution(int kind, double bound) const {
 // (the rtol ||b|| branch of KSP's rule can only stop GMRES earlier, i.e. less accurately); at such contraction both need the same ~4
 // applications per step, and the stationary iteration has no orthogonalisation, no Hessenberg problem and one fp32 reduction per
 // iteration instead of two fp64 ones (4-qubit system: 2.7 ms against 7.6 ms per 1000 steps, 2^5: 15 against 34).
-bool qd_handle::gmres_as_neumann(const qd::LaunchCfg& cfg) const {
+bool qd_handle::gmres_as_neumann(const LaunchCfg& cfg, const RowBound& b) const {
   if (!cfg.gmres || sol.stepper == QD_STEPPER_EE || opts.gmres_split != -1) return false;  // (gmres_split = 1 only forces the column path)
-  double dg, of;
-  row_bounds(&dg, &of);
-  double amax = 0.0;
-  for (double hh : sched_h) amax = std::max(amax, fabs(hh) / 2.0);
-  return latched_substitution(2, amax * (dg + of));
+  return latched_substitution(2, b.amax * (b.diag + b.off));
 }
 
 // Diagonal-split Neumann iteration (qd_col.hip): same fixed point and stopping rule, the diagonal of M on the left-hand side.  It
 // costs nothing per iteration, so "where it pays" is wherever the diagonal (level energies, decay) is a visible share of the row
 // bound: alpha (diag + off) is the contraction bound of the plain iteration, alpha off that of the split one.
-int qd_handle::neumann_split_on() const {
+int qd_handle::neumann_split_on(const RowBound& b) const {
   if (opts.neumann_split >= 0) return opts.neumann_split;
   if (S.dense) return 0;
-  double dg, of;
-  row_bounds(&dg, &of);
-  return dg >= 0.25 * of ? 1 : 0;
+  return b.diag >= 0.25 * b.off ? 1 : 0;
+}
+
+// The kernel family that serves a configuration, in order of precedence.  slot / col: the lean slot (2^4 / 2^5 Lindblad, coupled or
+// not) and lean column kernels may serve this use, where they are built for the system.
+Family qd_handle::pick_family(const LaunchCfg& cfg, bool slot, bool col) const {
+  if (precision == QD_PRECISION_F32MIXED) return Family::F32;
+  if (slot && cfg.var != 16 && lean64_available(S, opts)) return Family::Slot;
+  if (col) return Family::Col;
+  return cfg.var == 16 ? Family::Global : Family::General;
+}
+
+// One operator application: no solver and no stepper, so the lean kernels serve it wherever they are built - under explicit Euler
+// too, whose sweeps never run on them.
+Family qd_handle::apply_family(const LaunchCfg& cfg) const { return pick_family(cfg, true, cfg.var == 9 && collean_available(S, opts)); }
+
+// Which kernels a sweep of nb states runs on and with which linear solver.  The forward launch, the adjoint launch and
+// adjoint_reads_states all ask here, so that they cannot disagree; adjoint = the forward sweep's polynomial degree carries over.
+// Nothing of the handle changes except the latch of the two stand-in gates (latched_substitution): the split gate is asked first,
+// the Neumann gate only where it declines, in every plan.
+SweepPlan qd_handle::plan_sweep(int nb, bool adjoint) const {
+  SweepPlan p{};
+  RowBound b{0.0, 0.0, 0.0};
+  row_bounds(&b.diag, &b.off);
+  for (double hh : sched_h) b.amax = std::max(b.amax, fabs(hh) / 2.0);
+  const bool ee = sol.stepper == QD_STEPPER_EE, f32 = precision == QD_PRECISION_F32MIXED;
+  LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES);
+  // (the off-diagonal gate only where the lean column Krylov path runs: every other GMRES applies the whole row)
+  p.gated_poly = gmres_poly_degree(col_sweep(cfg, b) && cfg.gmres, b);
+  // (the adjoint sweep of an evaluation runs on the degree its forward sweep ran on: the tuner moves between the two, forward_finish)
+  if (adjoint && opts.gmres_poly == 0 && fwd_poly > 1 && p.gated_poly > 1) p.gated_poly = fwd_poly;
+  p.gmres_poly = p.tuner_poly = p.gated_poly;
+  p.solver = ee ? QD_SOLVER_NONE : cfg.gmres ? QD_SOLVER_KRYLOV : QD_SOLVER_NEUMANN;
+  p.neumann_split = neumann_split_on(b);
+  p.maxiter_factor = 1;
+  if (gmres_as_split(cfg, b, &p.kappa2)) {  // GMRES request served by the diagonal-split iteration of the lean column kernels
+    p.solver = QD_SOLVER_GMRES_AS_SPLIT;
+    cfg.gmres = 0;
+    cfg.lds = pick_config(S, nb, opts, false).lds;  // (the variant stays: only the Krylov solver's LDS goes)
+    p.neumann_split = p.stop_residual = 1;
+  } else if (gmres_as_neumann(cfg, b)) {
+    p.solver = QD_SOLVER_GMRES_AS_NEUMANN;
+    cfg = pick_config(S, nb, opts, false);  // (the whole configuration of a Neumann request, its team included)
+    p.gmres_poly = 1;
+  }
+  if (p.solver == QD_SOLVER_GMRES_AS_SPLIT || p.solver == QD_SOLVER_GMRES_AS_NEUMANN) {
+    p.standin_tau2 = (float)(opts.standin_tau * opts.standin_tau);
+    p.maxiter_factor = 3;  // (linearsolver_maxiter caps KRYLOV iterations: at the gate's contraction bound 0.3 thirty stationary iterations
+                           // reach what ten GMRES iterations reach in the worst case; the stopping rule ends the loop long before)
+    p.tuner_poly = 1;
+  }
+  p.cfg = cfg;  // (cfg.gmres is now what the kernel runs: SweepArgs::use_gmres)
+  const bool col = col_sweep(cfg, b);
+  p.family = pick_family(cfg, !ee, col);
+  p.team = cfg.var == 16 && cfg.team > 1 && !f32 ? cfg.team : 1;
+  p.need_big = cfg.var == 16;
+  // (the fp32-mixed GMRES and the fp64 one of the lean slot kernels always keep their basis in global memory [r6])
+  if (cfg.gmres == 2 || (cfg.gmres && (p.family == Family::F32 || p.family == Family::Slot)))
+    p.kry_doubles = col ? col_krylov_doubles(nb, col_slices(nb, tg.ntime, opts)) : krylov_doubles(S, nb);
+  return p;
 }
 
 // Does the adjoint sweep that follows a forward sweep of nb states read the stored states x_n (SweepArgs::traj), or only the primal
 // stages z?  States: explicit Euler (no stages), the dpdm penalty (second differences of x), the leakage penalty and the weighted-J
 // penalty (their adjoints are functions of x_n; on the lean column kernels the weighted Jmeasure's adjoint is a constant per row) -
 // and every kernel family whose adjoint kernel has not been written to do without (general / global-memory kernels).
-bool qd_handle::adjoint_reads_states(int nb, const qd::DevTarget* tgp) const {
+bool qd_handle::adjoint_reads_states(int nb, const qd::DevTarget* tgp, const SweepPlan* plan) const {
   if (sol.stepper == QD_STEPPER_EE || pen.gamma_penalty_dpdm > 1e-13) return true;
-  // (the same selection as adjoint_launch makes: the adjoint flag passed through)
-  LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES, /*adjoint=*/true);
-  if (gmres_as_split(cfg, nullptr)) cfg.gmres = 0;
-  else if (gmres_as_neumann(cfg)) cfg = pick_config(S, nb, opts, false, true);
+  const Family family = plan ? plan->family : plan_sweep(nb, true).family;  // (the plan adjoint_launch will make)
   const bool pen_on = pen.gamma_penalty > 1e-13;
   const bool wj = pen_on && tgp && pen.penalty_param > 1e-13;
   bool leak = false;
   for (int k = 0; k < S.Q; k++)
     if (pen_on && S.ness[k] < S.n[k]) leak = true;
-  const bool lean64 = cfg.var != 16 && lean64_available(S, opts);
-  if (precision == QD_PRECISION_F32MIXED || lean64) return wj || leak;
-  if (use_col(cfg)) return (wj && tgp->objective_type != QD_OBJ_JMEASURE) || leak;
+  if (family == Family::F32 || family == Family::Slot) return wj || leak;
+  if (family == Family::Col) return (wj && tgp->objective_type != QD_OBJ_JMEASURE) || leak;
   return true;
 }
 
@@ -842,7 +888,8 @@ int qd_handle::ensure_wj_weights() {
   return QD_OK;
 }
 
-static void fill_sweep(const qd_handle* h, SweepArgs& a, int nb, const DevTarget* tg) {
+int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const DevTarget* tg) {
+  const qd_handle* h = this;
   std::memset(&a, 0, sizeof a);
   a.S = h->S;
   if (tg) a.tg = *tg;
@@ -856,17 +903,21 @@ static void fill_sweep(const qd_handle* h, SweepArgs& a, int nb, const DevTarget
   a.Tfinal = h->dctl.Tfinal;
   a.stepper_ee = h->sol.stepper == QD_STEPPER_EE;
   a.linsolve = h->sol.linsolve;
-  a.maxiter = h->sol.maxiter;
+  a.maxiter = h->sol.maxiter * p.maxiter_factor;
   a.abstol = h->sol.abstol;
   a.reltol = h->sol.reltol;
   a.inv_abs2 = 1.0 / (a.abstol * a.abstol);
   a.rel2 = (float)(a.reltol * a.reltol);
-  a.gmres_poly = 1;  // (set by the launch once its kernel family is known: gmres_poly_degree)
+  a.gmres_poly = p.gmres_poly;
+  a.use_gmres = p.cfg.gmres;
+  a.stop_residual = p.stop_residual;
+  a.kappa2 = p.kappa2;
+  a.standin_tau2 = p.standin_tau2;
   a.col_noskip = !h->opts.col_skip;
   a.kry_tau2 = h->opts.krylov_tau * h->opts.krylov_tau;
   a.kry_restart = h->opts.krylov_restart;
   a.nslice = 1;
-  a.neumann_split = h->neumann_split_on();
+  a.neumann_split = p.neumann_split;
   // penalties that need target data are only active when a target has been set
   a.gamma_penalty = h->pen.gamma_penalty;
   a.penalty_param = tg ? h->pen.penalty_param : 0.0;
@@ -875,6 +926,16 @@ static void fill_sweep(const qd_handle* h, SweepArgs& a, int nb, const DevTarget
   a.leak_on = 0;
   for (int k = 0; k < h->S.Q; k++)
     if (h->S.ness[k] < h->S.n[k]) a.leak_on = 1;  // addLeakagePrevent, src/timestepper.cpp:28-32
+  last_poly = p.tuner_poly;
+  last_team = p.team;
+  last_solver = p.solver;
+  int r;
+  if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
+  a.kry = p.kry_doubles ? d_kry.p : nullptr;
+  if ((r = check_cfg(p.cfg))) return r;
+  if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
+    return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
+  return QD_OK;
 }
 
 // Time-sliced scheduling of a lean column sweep (qd_col.hip): scheduler words zeroed on the stream, carry buffer of the adjoint state.
@@ -932,20 +993,20 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   napply_zeroed = false;
   if ((r = refresh_tables())) return r;
   traj_valid = false;
-  const bool full = store && stores_full(nb, tgp);
+  const SweepPlan plan = plan_sweep(nb, false);
+  fwd_poly = plan.gated_poly;
+  // (the adjoint sweep's plan differs from this one in the carried-over degree only: the same family)
+  const bool full = store && (!stages_only || adjoint_reads_states(nb, tgp, &plan));
   if (store) {
     size_t nt;
     traj_doubles(nb, &nt);
     if (full && (r = d_traj.ensure(nt))) return r;
     if (ztraj_doubles(nb) && (r = d_ztraj.ensure(ztraj_doubles(nb)))) return r;
   }
-  {
-    LaunchCfg c0 = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES);
-    if (c0.var == 16 && (r = ensure_big(nb))) return r;
-  }
+  if (plan.need_big && (r = ensure_big(nb))) return r;
   if ((r = ensure_wj_weights())) return r;
   SweepArgs a;
-  fill_sweep(this, a, nb, tgp);
+  if ((r = prepare_sweep(a, plan, nb, tgp))) return r;
   a.x0 = dx0;
   a.xT = d_xT.p;
   a.traj = full ? d_traj.p : nullptr;
@@ -953,55 +1014,17 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   a.pen_out = d_pen;
   a.dpdm_out = d_dpdm;
   a.napply = d_napply;
-  LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES);
-  last_var = cfg.var;
-  a.gmres_poly = gmres_poly_degree(use_col(cfg) && cfg.gmres);
-  last_poly = a.gmres_poly;
-  fwd_poly = a.gmres_poly;
-  last_team = cfg.var == 16 && cfg.team > 1 && precision != QD_PRECISION_F32MIXED ? cfg.team : 1;
-  a.use_gmres = cfg.gmres;
-  last_solver = sol.stepper == QD_STEPPER_EE ? QD_SOLVER_NONE : cfg.gmres ? QD_SOLVER_KRYLOV : QD_SOLVER_NEUMANN;
-  if (gmres_as_split(cfg, &a.kappa2)) {  // GMRES request served by the diagonal-split iteration of the lean column kernels
-    last_solver = QD_SOLVER_GMRES_AS_SPLIT;
-    a.standin_tau2 = (float)(opts.standin_tau * opts.standin_tau);
-    cfg.gmres = 0;
-    a.use_gmres = 0;
-    a.neumann_split = 1;
-    a.stop_residual = 1;
-    a.maxiter *= 3;  // (linearsolver_maxiter caps KRYLOV iterations: at the gate's contraction bound 0.3 thirty stationary iterations
-                     // reach what ten GMRES iterations reach in the worst case; the stopping rule ends the loop long before)
-    last_poly = 1;
-    cfg.lds = pick_config(S, nb, opts, false).lds;
-  } else if (gmres_as_neumann(cfg)) {
-    last_solver = QD_SOLVER_GMRES_AS_NEUMANN;
-    a.standin_tau2 = (float)(opts.standin_tau * opts.standin_tau);
-    cfg = pick_config(S, nb, opts, false);
-    a.use_gmres = 0;
-    a.gmres_poly = 1;
-    a.maxiter *= 3;
-    last_poly = 1;
-    last_team = cfg.var == 16 && cfg.team > 1 && precision != QD_PRECISION_F32MIXED ? cfg.team : 1;
-  }
-  // (the fp32-mixed GMRES and the fp64 one of the lean slot kernels always keep their basis in global memory)
-  if (cfg.gmres == 2 || (cfg.gmres && (precision == QD_PRECISION_F32MIXED || (cfg.var != 16 && lean64_available(S, opts) && sol.stepper != QD_STEPPER_EE)))) {
-    if ((r = d_kry.ensure(use_col(cfg) ? col_krylov_doubles(nb, col_slices(nb, tg.ntime, opts)) : krylov_doubles(S, nb)))) return r;
-    a.kry = d_kry.p;
-  }
-  if ((r = check_cfg(cfg))) return r;
   if (!napply_zeroed) QD_HIP(hipMemsetAsync(d_napply, 0, sizeof(unsigned long long), stream));
   QD_HIP(hipEventRecord(ev0, stream));
-  // (2^4 / 2^5 Lindblad: the lean slot kernels, coupled or not; their Krylov solver keeps its basis in global memory [r6])
-  const bool lean64 = cfg.var != 16 && lean64_available(S, opts) && sol.stepper != QD_STEPPER_EE;
-  if (a.ztraj) ztraj_fmt = precision == QD_PRECISION_F32MIXED ? 1 : lean64 ? 2 : use_col(cfg) ? 3 : 0;
-  if (precision == QD_PRECISION_F32MIXED && S.hasJ && a.use_gmres)
-    return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
+  if (a.ztraj) ztraj_fmt = plan.stage_layout();
   take_kernel(0);
-  if (precision == QD_PRECISION_F32MIXED) QD_HIP(launch_forward_f32(a, opts, stream));
-  else if (lean64) QD_HIP(launch_forward_lean64(a, opts, stream));
-  else if (use_col(cfg)) {
-    if ((r = arm_slices(a, nb, 0))) return r;
-    QD_HIP(launch_forward_col(a, stream));
-  } else QD_HIP(launch_forward(a, cfg, stream));
+  if (plan.family == Family::Col && (r = arm_slices(a, nb, 0))) return r;
+  switch (plan.family) {
+    case Family::F32: QD_HIP(launch_forward_f32(a, opts, stream)); break;
+    case Family::Slot: QD_HIP(launch_forward_lean64(a, opts, stream)); break;
+    case Family::Col: QD_HIP(launch_forward_col(a, stream)); break;
+    default: QD_HIP(launch_forward(a, plan.cfg, stream));  // General and Global: the variant says which
+  }
   last_kernel[0] = take_kernel(0);
   QD_HIP(hipEventRecord(ev1, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(h_sched.p, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
@@ -1174,69 +1197,30 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   int r;
   const size_t ncol = (size_t)nsub * 2 * S.Q;
   if ((r = d_coeff.ensure((size_t)nb * ncol)) || (r = d_coeffsum.ensure(ncol))) return r;
-  {
-    LaunchCfg c0 = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES, true);
-    if (c0.var == 16 && (r = ensure_big(nb))) return r;
-  }
+  const SweepPlan plan = plan_sweep(nb, true);
+  if (plan.need_big && (r = ensure_big(nb))) return r;
   if ((r = ensure_wj_weights())) return r;
-  SweepArgs a;
-  fill_sweep(this, a, nb, tgp);
   const bool have_states = pending_store ? pending_full : traj_full;
-  if (!have_states && adjoint_reads_states(nb, tgp))
+  if (!have_states && adjoint_reads_states(nb, tgp, &plan))
     return fail(QD_ERR_STATE, "qd_adjoint: the forward sweep stored the primal stages only, this adjoint sweep needs the states");
+  if (ztraj_doubles(nb) && ztraj_fmt != plan.stage_layout())
+    return fail(QD_ERR_STATE, "qd_adjoint: the primal stages were stored by another kernel family (options or precision changed since the forward sweep): repeat the forward sweep");
+  SweepArgs a;
+  if ((r = prepare_sweep(a, plan, nb, tgp))) return r;
   a.traj = have_states ? d_traj.p : nullptr;
   a.ztraj = ztraj_doubles(nb) ? d_ztraj.p : nullptr;
   a.xbarT = dxbarT;
   a.jbar = djbar;
   a.coeff = d_coeff.p;
-  LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES, /*adjoint=*/true);
-  a.gmres_poly = gmres_poly_degree(use_col(cfg) && cfg.gmres);
-  // (the adjoint sweep of an evaluation runs on the degree its forward sweep ran on: the tuner moves between the two, forward_finish)
-  if (opts.gmres_poly == 0 && fwd_poly > 1 && a.gmres_poly > 1) a.gmres_poly = fwd_poly;
-  last_poly = a.gmres_poly;
-  last_team = cfg.var == 16 && cfg.team > 1 && precision != QD_PRECISION_F32MIXED ? cfg.team : 1;
-  a.use_gmres = cfg.gmres;
-  last_solver = sol.stepper == QD_STEPPER_EE ? QD_SOLVER_NONE : cfg.gmres ? QD_SOLVER_KRYLOV : QD_SOLVER_NEUMANN;
-  if (gmres_as_split(cfg, &a.kappa2)) {
-    last_solver = QD_SOLVER_GMRES_AS_SPLIT;
-    a.standin_tau2 = (float)(opts.standin_tau * opts.standin_tau);
-    cfg.gmres = 0;
-    a.use_gmres = 0;
-    a.neumann_split = 1;
-    a.stop_residual = 1;
-    a.maxiter *= 3;
-    last_poly = 1;
-    cfg.lds = pick_config(S, nb, opts, false, true).lds;
-  } else if (gmres_as_neumann(cfg)) {
-    last_solver = QD_SOLVER_GMRES_AS_NEUMANN;
-    a.standin_tau2 = (float)(opts.standin_tau * opts.standin_tau);
-    cfg = pick_config(S, nb, opts, false, true);
-    a.use_gmres = 0;
-    a.gmres_poly = 1;
-    a.maxiter *= 3;
-    last_poly = 1;
-    last_team = cfg.var == 16 && cfg.team > 1 && precision != QD_PRECISION_F32MIXED ? cfg.team : 1;
-  }
-  // (the fp32-mixed GMRES and the fp64 one of the lean slot kernels always keep their basis in global memory)
-  if (cfg.gmres == 2 || (cfg.gmres && (precision == QD_PRECISION_F32MIXED || (cfg.var != 16 && lean64_available(S, opts) && sol.stepper != QD_STEPPER_EE)))) {
-    if ((r = d_kry.ensure(use_col(cfg) ? col_krylov_doubles(nb, col_slices(nb, tg.ntime, opts)) : krylov_doubles(S, nb)))) return r;
-    a.kry = d_kry.p;
-  }
-  if ((r = check_cfg(cfg))) return r;
   QD_HIP(hipEventRecord(ev2, stream));
-  // (2^4 / 2^5 Lindblad: the lean slot kernels, coupled or not; their Krylov solver keeps its basis in global memory [r6])
-  const bool lean64 = cfg.var != 16 && lean64_available(S, opts) && sol.stepper != QD_STEPPER_EE;
-  if (a.ztraj && ztraj_fmt != (precision == QD_PRECISION_F32MIXED ? 1 : lean64 ? 2 : use_col(cfg) ? 3 : 0))
-    return fail(QD_ERR_STATE, "qd_adjoint: the primal stages were stored by another kernel family (options or precision changed since the forward sweep): repeat the forward sweep");
-  if (precision == QD_PRECISION_F32MIXED && S.hasJ && a.use_gmres)
-    return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0)");
   take_kernel(1);
-  if (precision == QD_PRECISION_F32MIXED) QD_HIP(launch_adjoint_f32(a, opts, stream));
-  else if (lean64) QD_HIP(launch_adjoint_lean64(a, opts, stream));
-  else if (use_col(cfg)) {
-    if ((r = arm_slices(a, nb, 1))) return r;
-    QD_HIP(launch_adjoint_col(a, stream));
-  } else QD_HIP(launch_adjoint(a, cfg, stream));
+  if (plan.family == Family::Col && (r = arm_slices(a, nb, 1))) return r;
+  switch (plan.family) {
+    case Family::F32: QD_HIP(launch_adjoint_f32(a, opts, stream)); break;
+    case Family::Slot: QD_HIP(launch_adjoint_lean64(a, opts, stream)); break;
+    case Family::Col: QD_HIP(launch_adjoint_col(a, stream)); break;
+    default: QD_HIP(launch_adjoint(a, plan.cfg, stream));  // General and Global: the variant says which
+  }
   last_kernel[1] = take_kernel(1);
   QD_HIP(hipEventRecord(ev3, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));

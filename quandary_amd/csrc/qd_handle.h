@@ -73,18 +73,51 @@ struct HBuf {
   }
 };
 
+// Kernel family of a sweep or an operator application.  The values 0-3 are also the layout tags of the stored primal stages
+// (qd_handle::ztraj_fmt): 1 = fp32 pairs, 0 / 2 / 3 = fp64 pairs in the element order of the general / slot / lean column kernels.
+// General: one workgroup per state, vectors in LDS (qd_device.h); F32 / Slot: slot kernels in fp32-mixed / fp64 ("lean64", qd_q32.hip);
+// Col: lean column kernels (qd_col.hip); Global: vectors in global memory, teams of workgroups (qd_big.h, variant 16).
+enum class Family { General = 0, F32 = 1, Slot = 2, Col = 3, Global = 4 };
+
+// Gershgorin bounds of a row of M for the current parameters (qd_handle::row_bounds) and the largest alpha = |h| / 2 of the step
+// schedule: what every solver gate looks at, computed once per plan
+struct RowBound { double diag, off, amax; };
+
+// Everything the host decides about one sweep before it launches it (qd_handle::plan_sweep)
+struct SweepPlan {
+  Family family;
+  LaunchCfg cfg;       // final configuration (a stand-in for GMRES has re-picked it)
+  int solver;          // QD_SOLVER_*: the iteration that solves the linear systems (qd_last_solver)
+  int neumann_split, stop_residual, maxiter_factor;  // SweepArgs fields of the same names (maxiter: x linearsolver_maxiter); use_gmres = cfg.gmres
+  double kappa2;
+  float standin_tau2;
+  int gated_poly;      // degree the contraction gate gives the Krylov solver of the picked configuration (adjoint: the forward sweep's, fwd_poly)
+  int gmres_poly;      // degree handed to the kernel
+  int tuner_poly;      // degree the tuner accounts the sweep's applications to (last_poly; 1 = not a preconditioned Krylov sweep)
+  int team;            // workgroups per initial condition (qd_last_team)
+  size_t kry_doubles;  // Krylov basis in global memory (SweepArgs::kry), 0 = none
+  bool need_big;       // ensure_big before the launch
+  // the global-memory kernels store the stages in the element order of the general ones
+  Family stage_layout() const { return family == Family::Global ? Family::General : family; }
+};
+
 }  // namespace qd
 
 struct qd_handle {
   int device = 0;
   int precision = QD_PRECISION_F64;  // qd_set_precision
   qd::TuneOpts opts;                 // qd_set_option (+ environment overrides read at qd_create)
-  bool use_col(const qd::LaunchCfg& cfg) const;  // the sweep runs on the lean column kernels (qd_col.hip)
-  int neumann_split_on() const;      // diagonal-split Neumann iteration for the current parameters
+  // ---- which kernel family and which linear solver a sweep runs on: decided once per launch, in plan_sweep (qd_handle.cpp) ----
+  qd::SweepPlan plan_sweep(int nb, bool adjoint) const;
+  qd::Family apply_family(const qd::LaunchCfg& cfg) const;  // the same choice for one operator application (qd_apply_rhs)
+  // named steps of plan_sweep, described where they are defined; nothing else calls them
+  qd::Family pick_family(const qd::LaunchCfg& cfg, bool slot, bool col) const;
+  bool col_sweep(const qd::LaunchCfg& cfg, const qd::RowBound& b) const;  // the sweep runs on the lean column kernels (qd_col.hip)
+  int neumann_split_on(const qd::RowBound& b) const;  // diagonal-split Neumann iteration for the current parameters
   // linearsolver_type = gmres served by the diagonal-split iteration of the lean column kernels under GMRES's stopping rule;
   // *kappa2 = (1 + max alpha |D|)^2, the factor between the squared update norm and the bound of the squared residual
-  bool gmres_as_split(const qd::LaunchCfg& cfg, double* kappa2) const;
-  bool gmres_as_neumann(const qd::LaunchCfg& cfg) const;  // ... by the plain Neumann iteration of any other kernel family
+  bool gmres_as_split(const qd::LaunchCfg& cfg, const qd::RowBound& b, double* kappa2) const;
+  bool gmres_as_neumann(const qd::LaunchCfg& cfg, const qd::RowBound& b) const;  // ... by the plain Neumann iteration of any other kernel family
   // the decision of the two gates, latched per handle: -1 undecided, 0 Krylov kernels, 1 diagonal-split iteration, 2 Neumann iteration
   mutable int sub_latch = -1;
   bool params_set = false;  // qd_set_params has been called (the gates look at the control amplitudes)
@@ -147,7 +180,7 @@ struct qd_handle {
   unsigned long long* d_napply = nullptr;
   int last_nb = 0;
   bool traj_valid = false;
-  int ztraj_fmt = 0;  // layout of the stored primal stages: 1 = fp32 pairs (fp32-mixed), 0 / 2 / 3 = fp64 pairs written by the general / 2^5 / lean column kernels (element order of the family)
+  qd::Family ztraj_fmt = qd::Family::General;  // layout of the stored primal stages = the family that wrote them (SweepPlan::stage_layout)
   double last_mean_applies = 0.0, last_fwd_ms = 0.0, last_adj_ms = 0.0;
   bool accumulate_fwd_ms = false;  // chunked re-propagation (qd_optim_adjoint_local): add the chunks' forward times up
 
@@ -156,9 +189,9 @@ struct qd_handle {
   mutable double hmax_cache = -1.0;  // max |h(I)| over the level combinations (system constant, computed on first use)
   double control_amplitude_bound(int k) const;       // max_t |p_k(t)|, |q_k(t)| for the current parameters
   void row_bounds(double* diag, double* off) const;  // Gershgorin bounds of a row of M over all sub-steps (current parameters)
-  int gmres_poly_degree(bool lean_col) const;  // > 1 where the Neumann series provably contracts for the current parameters, else 1
+  int gmres_poly_degree(bool lean_col, const qd::RowBound& b) const;  // > 1 where the Neumann series provably contracts for the current parameters, else 1
   // degree of the polynomial preconditioner, tuned from sweep to sweep (forward_finish): smallest degree with one Krylov vector per solve
-  int poly_cur = 6, poly_lo = 1, poly_hi = 0, last_poly = 1, last_var = 0, poly_steps = 0;
+  int poly_cur = 6, poly_lo = 1, poly_hi = 0, last_poly = 1, poly_steps = 0;
   int fwd_poly = 0;  // degree the last forward sweep ran on (the adjoint sweep of the same evaluation keeps it)
   int poly_start() const { return S.dim <= 1024 ? 3 : 6; }  // first degree the tuner tries (small systems contract fast)
   int poly_slow = 0;         // consecutive sweeps of a frozen degree with more than 1.5 Krylov vectors per solve
@@ -180,7 +213,9 @@ struct qd_handle {
   // trajectory memory.  traj_full: d_traj holds the states x_n of the last stored sweep (qd_get_state, qd_get_observables, penalties
   // with state-dependent adjoints, explicit Euler).
   bool stages_only = false, traj_full = false, pending_full = false;
-  bool adjoint_reads_states(int nb, const qd::DevTarget* tg) const;
+  bool adjoint_reads_states(int nb, const qd::DevTarget* tg, const qd::SweepPlan* plan = nullptr) const;  // plan: the sweep's, where the caller has it
+  // what the two launches share once the plan is made: SweepArgs from the handle and the plan, Krylov buffer, the records of the sweep
+  int prepare_sweep(qd::SweepArgs& a, const qd::SweepPlan& p, int nb, const qd::DevTarget* tg);
   bool stores_full(int nb, const qd::DevTarget* tg) const { return !stages_only || adjoint_reads_states(nb, tg); }
   // adjoint sweep; dxbarT/djbar device pointers; coefficient sums accumulate into d_coeffsum
   int adjoint_dev(const double* dxbarT, const double* djbar, int nb, const qd::DevTarget* tg, bool accumulate);

@@ -228,7 +228,7 @@ size_t col_krylov_doubles(int nb, int nslice);  // size of SweepArgs::kry for th
 hipError_t launch_forward_col(const SweepArgs& a, hipStream_t st);
 hipError_t launch_adjoint_col(const SweepArgs& a, hipStream_t st);
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st);
-LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false, bool adjoint = false);
+LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false);
 size_t krylov_doubles(const DevSys& S, int nb);
 size_t big_work_doubles(const DevSys& S, int nb);
 hipError_t launch_big_table(const DevSys& S, double* ecoef, unsigned* edig, hipStream_t st);

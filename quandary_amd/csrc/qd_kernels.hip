@@ -443,7 +443,7 @@ static const VarInfo kVar[NVARIANTS] = {var_info<0>(), var_info<1>(),  var_info<
 int variant_max_block(int var) { return (var >= 0 && var < NVARIANTS) ? kVar[var].maxb : 0; }
 
 void big_team(const DevSys& S, int nb, const TuneOpts& o, int& team, int& spread);
-LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres, bool adjoint) {
+LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres) {
   LaunchCfg c{};
   const int dim = S.dim;
   bool qubit = true;
