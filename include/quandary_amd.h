@@ -264,7 +264,8 @@ int qd_last_team(const qd_handle* h);
 int qd_last_solver(const qd_handle* h);
 /* Test hook: the kernel instantiation last launched on this handle for `which` = 0 (forward sweep), 1 (adjoint sweep) or 2 (operator
  * application, qd_apply_rhs), spelled as `nm -C` prints it without namespace and arguments, e.g. "k_forward_col<3, 8, true, false, false,
- * false>"; "" before the first such launch.  The string belongs to the handle and stays valid until its next launch of that role. */
+ * false>" (a system with dipole-dipole coupling on the lean column kernels: "k_forward_colj<2, 5, true, true, false, false>"); "" before
+ * the first such launch.  The string belongs to the handle and stays valid until its next launch of that role. */
 const char* qd_last_kernel(const qd_handle* h, int which);
 /* Measurement hook for the secondary (fp64 vector) roofline: runs a register-only
  * v_fma_f64 micro-benchmark on the device and returns the sustained TFLOP/s in

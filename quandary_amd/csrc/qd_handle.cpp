@@ -728,8 +728,13 @@ int qd_handle::gmres_poly_degree(bool lean_col, const RowBound& b) const {
 // the lean column kernels: the stationary iterations, and [r6] the Krylov solver wherever its polynomial preconditioner is on - under
 // the off-diagonal gate of gmres_poly_degree(true).  Without it (KSPGMRES + PCNONE iteration for iteration) or with the option
 // no_col_krylov a gmres request stays on the general column kernel, preconditioned only where the full-row gate holds.
-bool qd_handle::col_sweep(const LaunchCfg& cfg, const RowBound& b) const {
+// Systems with dipole-dipole coupling (S.hasJ: the k_*_colj kernels of qd_colj.hip) are built in the diagonal-split form only - the
+// Krylov solver, and the stationary iteration with split = the plan's neumann_split set.  THE rule for what that set does not cover: a
+// coupled sweep on the plain Neumann iteration (split = 0: the option neumann_split = 0, or a row bound whose diagonal is small,
+// neumann_split_on) runs where it ran before those kernels existed, on the general column kernel.
+bool qd_handle::col_sweep(const LaunchCfg& cfg, const RowBound& b, int split) const {
   if (!(precision == QD_PRECISION_F64 && cfg.var == 9 && collean_available(S, opts) && sol.stepper != QD_STEPPER_EE)) return false;
+  if (S.hasJ && !cfg.gmres && !split) return false;
   return !cfg.gmres || (cfg.gmres == 2 && !opts.no_col_krylov && gmres_poly_degree(true, b) > 1);
 }
 
@@ -819,13 +824,13 @@ SweepPlan qd_handle::plan_sweep(int nb, bool adjoint) const {
   for (double hh : sched_h) b.amax = std::max(b.amax, fabs(hh) / 2.0);
   const bool ee = sol.stepper == QD_STEPPER_EE, f32 = precision == QD_PRECISION_F32MIXED;
   LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES);
+  p.neumann_split = neumann_split_on(b);
   // (the off-diagonal gate only where the lean column Krylov path runs: every other GMRES applies the whole row)
-  p.gated_poly = gmres_poly_degree(col_sweep(cfg, b) && cfg.gmres, b);
+  p.gated_poly = gmres_poly_degree(col_sweep(cfg, b, p.neumann_split) && cfg.gmres, b);
   // (the adjoint sweep of an evaluation runs on the degree its forward sweep ran on: the tuner moves between the two, forward_finish)
   if (adjoint && opts.gmres_poly == 0 && fwd_poly > 1 && p.gated_poly > 1) p.gated_poly = fwd_poly;
   p.gmres_poly = p.tuner_poly = p.gated_poly;
   p.solver = ee ? QD_SOLVER_NONE : cfg.gmres ? QD_SOLVER_KRYLOV : QD_SOLVER_NEUMANN;
-  p.neumann_split = neumann_split_on(b);
   p.maxiter_factor = 1;
   if (gmres_as_split(cfg, b, &p.kappa2)) {  // GMRES request served by the diagonal-split iteration of the lean column kernels
     p.solver = QD_SOLVER_GMRES_AS_SPLIT;
@@ -844,7 +849,7 @@ SweepPlan qd_handle::plan_sweep(int nb, bool adjoint) const {
     p.tuner_poly = 1;
   }
   p.cfg = cfg;  // (cfg.gmres is now what the kernel runs: SweepArgs::use_gmres)
-  const bool col = col_sweep(cfg, b);
+  const bool col = col_sweep(cfg, b, p.neumann_split);
   p.family = pick_family(cfg, !ee, col);
   p.team = cfg.var == 16 && cfg.team > 1 && !f32 ? cfg.team : 1;
   p.need_big = cfg.var == 16;

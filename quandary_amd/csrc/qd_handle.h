@@ -112,7 +112,8 @@ struct qd_handle {
   qd::Family apply_family(const qd::LaunchCfg& cfg) const;  // the same choice for one operator application (qd_apply_rhs)
   // named steps of plan_sweep, described where they are defined; nothing else calls them
   qd::Family pick_family(const qd::LaunchCfg& cfg, bool slot, bool col) const;
-  bool col_sweep(const qd::LaunchCfg& cfg, const qd::RowBound& b) const;  // the sweep runs on the lean column kernels (qd_col.hip)
+  // the sweep runs on the lean column kernels (qd_col.hip, coupled systems qd_colj.hip); split = the plan's neumann_split
+  bool col_sweep(const qd::LaunchCfg& cfg, const qd::RowBound& b, int split) const;
   int neumann_split_on(const qd::RowBound& b) const;  // diagonal-split Neumann iteration for the current parameters
   // linearsolver_type = gmres served by the diagonal-split iteration of the lean column kernels under GMRES's stopping rule;
   // *kappa2 = (1 + max alpha |D|)^2, the factor between the squared update norm and the bound of the squared residual
