@@ -275,15 +275,17 @@ struct ColLean {
 
   // y = M x (TRANS = false) or M^T x at slot j (ColStencil::apply of qd_device.h; its S.hasJ block = HJ here)
   // NODIAG: only the off-diagonal part C = M - diag(M) (the diagonal-split solver applies the diagonal in closed form)
+  // acc: added to the result (the accumulators start there: no extra instruction)
   template <bool TRANS, bool NODIAG = false>
-  __device__ __forceinline__ double2 apply(const StepC<Q>& c, int j, const double2 own, const double2 prev, const double2 next) const {
-    double ar = 0.0, ai = 0.0;
+  __device__ __forceinline__ double2 apply(const StepC<Q>& c, int j, const double2 own, const double2 prev, const double2 next,
+                                           const double2* acc = nullptr) const {
+    double ar = acc ? acc->x : 0.0, ai = acc ? acc->y : 0.0;
     if (!NODIAG) {
       double dwj, ddj;
       diag(j, dwj, ddj);
       if (TRANS) dwj = -dwj;
-      ar = fma(dwj, own.y, ddj * own.x);
-      ai = fma(-dwj, own.x, ddj * own.y);
+      ar = fma(dwj, own.y, acc ? fma(ddj, own.x, ar) : ddj * own.x);
+      ai = fma(-dwj, own.x, acc ? fma(ddj, own.y, ai) : ddj * own.y);
     }
 #pragma unroll
     for (int k = 0; k < Q; k++) {
@@ -474,9 +476,18 @@ struct ColTeam {
     }
   }
 
-  template <bool TRANS>
-  __device__ __forceinline__ void set_alpha(double alpha) {
+  // FOLD (the forward kernels of the diagonal-split stationary solver, stage()): the step size is folded into the pass coefficients -
+  // the thread's T1 factor g1u here, recomputed from alpha (never rescaled: a time-sliced sweep stays bit-identical to an unsliced one),
+  // the sub-step's p, q (cs, sn) in stage().  (Without SPLIT the diagonal dw, dd would need the same; scaled in place by the ratio of
+  // the step sizes of a composite stepper it would depend on the workgroup's task history, recomputed it costs more than it saves.)
+  template <bool TRANS, bool FOLD = false>
+  __device__ __forceinline__ void set_alpha(const DevSys& S, double alpha) {
     if (alpha == palpha) return;  // (uniform)
+    if constexpr (FOLD) {
+      static_assert(!TRANS && SPLIT, "the forward operator of the diagonal-split solver");
+#pragma unroll
+      for (int k = 0; k < Q; k++) st.g1u[k] = (alpha * S.g1off[k]) * st.su[k];
+    }
     palpha = alpha;
 #pragma unroll
     for (int j = 0; j < (SPLIT ? EPT : 0); j++) {
@@ -573,8 +584,23 @@ struct ColTeam {
   // (the primal stage the adjoint sweep reads) and x_{n+1} = 2 z - x.  Returns the RHS applications (passes).
   // In place of GMRES (A.stop_residual): threshold max(rtol^2 ||b||^2, abstol^2) / kappa^2 with ||b||^2 >= ||y_0||^2 (|1 - alpha D| >= 1:
   // the diagonal of M has a non-positive real part) taken from the first pass - never looser than the rule it stands for.
+  // SPLIT: the step size is folded into the coefficients (set_alpha<false, true> has scaled the thread's part): a pass forms
+  // x + alpha C z with its accumulators started at x - two fp64 instructions per element less.
   __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, const double2 (&x)[EPT], double2 (&z)[EPT]) {
     const double sc = A.inv_abs2 / (alpha * alpha);
+    StepC<Q> ca = c;  // (alpha p, alpha q, alpha cs, alpha sn: scaled in VALU once per sub-step, back to scalar registers)
+#pragma unroll
+    for (int k = 0; k < (SPLIT ? Q : 0); k++) {
+      ca.p[k] = to_scalar(alpha * c.p[k]);
+      ca.q[k] = to_scalar(alpha * c.q[k]);
+    }
+    if constexpr (HJ && SPLIT) {
+#pragma unroll
+      for (int p = 0; p < ST::NP; p++) {
+        ca.cs[p] = to_scalar(alpha * c.cs[p]);
+        ca.sn[p] = to_scalar(alpha * c.sn[p]);
+      }
+    }
     float rel2 = A.rel2, thr = 1.f, d0 = 1.f, dprev = 1.f;
 #pragma unroll
     for (int j = 0; j < EPT; j++) z[j] = x[j];
@@ -587,10 +613,14 @@ struct ColTeam {
 #pragma unroll
       for (int j = 0; j < EPT; j++) {
         const double2 own = z[j];
-        const double2 t = st.template apply<false, SPLIT>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j]);
         double2 w;
-        w.x = fma(alpha, t.x, x[j].x);
-        w.y = fma(alpha, t.y, x[j].y);
+        if constexpr (SPLIT) {
+          w = st.template apply<false, true>(ca, j, own, prev, z[j + 1 < EPT ? j + 1 : j], &x[j]);  // x + alpha C z
+        } else {
+          const double2 t = st.template apply<false, false>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j]);
+          w.x = fma(alpha, t.x, x[j].x);
+          w.y = fma(alpha, t.y, x[j].y);
+        }
         if (SPLIT) w = make_double2(fma(pr[SPLIT ? j : 0], w.x, -pi[SPLIT ? j : 0] * w.y), fma(pr[SPLIT ? j : 0], w.y, pi[SPLIT ? j : 0] * w.x));
         const double dx = own.x - w.x, dy = own.y - w.y;
         dl = fma(dx, dx, fma(dy, dy, dl));
@@ -1114,7 +1144,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   for (int s = s_lo; s < s_hi; s++) {
     StepC<Q> c;
     load_step_k<Q>(A.ctl + (size_t)s * A.cs, c, HJ);
-    if (SPLIT) tm.template set_alpha<false>(0.5 * c.h);
+    if (SPLIT) tm.template set_alpha<false, SPLIT && !KRY>(S, 0.5 * c.h);
     if (A.traj) store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, x, true);
     // the sub-step in stage form (ColTeam::stage): x is the right-hand side of the solve and stays in registers
     tm.publish(x);
@@ -1276,7 +1306,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
     StepC<Q> c;
     load_step_k<Q>(A.ctl + (size_t)s * A.cs, c, HJ);
     // ImplMidpoint::evolveBWD (timestepper.cpp:631-694); the primal stage z of the sub-step was stored by the forward sweep
-    if (SPLIT) tm.template set_alpha<true>(0.5 * c.h);
+    if (SPLIT) tm.template set_alpha<true>(S, 0.5 * c.h);
     double2 kb[EPT];  // adjoint stage: (I - h/2 M)^T kbar = xbar ; kbar *= h
     if constexpr (KRY) tm.template kry_solve<true>(A, c, 0.5 * c.h, xb, kb);
     else tm.template neumann<true>(A, c, 0.5 * c.h, xb, kb);
