@@ -4,12 +4,16 @@
 //   #define QD_COLK(base) base##_col   /  base##_colj      (k_forward, k_adjoint, k_apply)
 //   #define QD_COL_HJ false            /  true
 // The kernels are defined here, once per unit, as __global__ templates over <Q, EPT, SPLIT, USLOT, SKIP, KRY> / <Q, EPT, SPLIT>: the
-// coupling is part of the kernel's NAME, not a template argument of it.
+// coupling is part of the kernel's NAME, not a template argument of it.  So are their launchers (the end of this file): which
+// instantiation a sweep runs is written once, for both units and both directions.
 #pragma once
 #if !defined(QD_COLK) || !defined(QD_COL_HJ)
 #error "define QD_COLK and QD_COL_HJ before including qd_col.h"
 #endif
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <type_traits>
 
 #include "qd_device.h"
 
@@ -1402,18 +1406,15 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_apply)(const D
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side shared by the launchers of qd_col.hip and qd_colj.hip
+// host side: the launchers, one text for both units - each instantiates them for its own kernels (QD_COLK) and coupling flag (QD_COL_HJ)
 // ---------------------------------------------------------------------------------------------
-int col_cu_count();
-// the same three entry points for systems with dipole-dipole coupling (qd_colj.hip); launch_*_col forward to them where S.hasJ
-hipError_t launch_forward_colj(const SweepArgs& a, hipStream_t st);
-hipError_t launch_adjoint_colj(const SweepArgs& a, hipStream_t st);
+// the entry points for systems with dipole-dipole coupling (qd_colj.hip); launch_sweep_col / launch_apply_col forward to them where S.hasJ
+hipError_t launch_sweep_colj(const SweepArgs& a, bool adjoint, hipStream_t st);
 hipError_t launch_apply_colj(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
 
-template <typename K>
-static hipError_t set_lds_col(K kern, size_t bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+#define QD_COL_STR_(x) #x
+#define QD_COL_STR(x) QD_COL_STR_(x)
+#define QD_COLK_NAME(base) QD_COL_STR(QD_COLK(base))  // "k_forward_col" / "k_forward_colj": the name note_kernel records
 
 // the columns of a wave share the level indices of every oscillator but the stride-1 one (ColLean's USLOT)
 template <int EPT>
@@ -1428,14 +1429,78 @@ static bool col_uslot(const DevSys& S) {
 template <typename K>
 static int col_grid(K kern, const SweepArgs& a, int threads, size_t lds) {
   if (!a.sched) return a.nb;
-  int per_cu = 1, dev = 0;
-  hipDeviceProp_t prop;
+  int per_cu = 1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  int ncu = col_cu_count();
-  (void)dev;
-  (void)prop;
   if (a.use_gmres) per_cu = std::min(per_cu, 2);  // (col_krylov_doubles)
-  return std::min(a.nb * a.nslice, per_cu * ncu);
+  return std::min(a.nb * a.nslice, per_cu * cu_count());
 }
+
+// One sweep kernel, forward or adjoint, of the instantiation <Q, EPT, SPLIT, USLOT, SKIP, KRY>: the two kernels of an instantiation are a
+// pair (the adjoint one reads the primal stages in the element order the forward one wrote), so the direction is the only thing left open.
+template <int Q, int EPT, bool SPLIT, bool USLOT, bool SKIP, bool KRY>
+static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
+  typedef ColLean<Q, EPT> ST;
+  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0);
+  const int threads = 64 * (ST::ncols(a.S.N) / EPT);
+  auto kf = adjoint ? QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY> : QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
+  hipError_t e = set_lds(kf, lds);
+  if (e != hipSuccess) return e;
+  note_kernel(adjoint ? 1 : 0, adjoint ? QD_COLK_NAME(k_adjoint) : QD_COLK_NAME(k_forward), Q, EPT, SPLIT, USLOT, SKIP, KRY);
+  hipLaunchKernelGGL(kf, dim3(col_grid(kf, a, threads, lds)), dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
+
+// The instantiation a sweep runs, from the run-time facts - the same for both directions.  Built: the Krylov solver (SweepArgs::use_gmres)
+// in the diagonal-split form that tests every pass; the stationary iteration in the plain and the diagonal-split form (neumann_split), each
+// with and without SKIP; every one of them in both USLOT forms.  With coupling (QD_COL_HJ) the diagonal-split forms without SKIP only: a
+// coupled sweep that asks for the plain Neumann iteration is never planned (qd_handle::col_sweep) and is an invalid value here.
+template <int Q, int EPT>
+static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
+  const bool uslot = col_uslot<EPT>(a.S);
+  auto go = [&](auto split, auto skip, auto kry) {
+    constexpr bool SPLIT = decltype(split)::value, SKIP = decltype(skip)::value, KRY = decltype(kry)::value;
+    return uslot ? col_launch<Q, EPT, SPLIT, true, SKIP, KRY>(a, adjoint, st) : col_launch<Q, EPT, SPLIT, false, SKIP, KRY>(a, adjoint, st);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (a.use_gmres) return go(yes, no, yes);
+  if constexpr (QD_COL_HJ) {
+    return a.neumann_split ? go(yes, no, no) : hipErrorInvalidValue;
+  } else {
+    // (SKIP: stopping tests skipped, see ColTeam::stage)
+    // (implicit midpoint only: the predictor compares the pass count of a sub-step with its predecessor's, and the sub-steps of a composite
+    //  step differ in size - IMR4 / IMR8 test every pass; nothing of this lives in the kernels)
+    const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;
+    if (a.neumann_split) return skip ? go(yes, yes, no) : go(yes, no, no);
+    return skip ? go(no, yes, no) : go(no, no, no);
+  }
+}
+
+// One operator application.  SPLIT selects the kernel family that re-derives the diagonal from its compact form (uncoupled: the option
+// neumann_split = 1, test coverage); the coupled kernels are built in that form only and their entry point passes split = true.
+template <int Q, int EPT>
+static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const double* x, double* y, int nb, bool split, hipStream_t st) {
+  typedef ColLean<Q, EPT> ST;
+  const size_t lds = ST::lds_bytes(S.N);
+  auto kf = QD_COLK(k_apply)<Q, EPT, true>;
+  if constexpr (!QD_COL_HJ)
+    if (!split) kf = QD_COLK(k_apply)<Q, EPT, false>;
+  hipError_t e = set_lds(kf, lds);
+  if (e != hipSuccess) return e;
+  note_kernel(2, QD_COLK_NAME(k_apply), Q, EPT, split);
+  hipLaunchKernelGGL(kf, dim3(nb), dim3(64 * (ST::ncols(S.N) / EPT)), lds, st, S, ctlrow, tr, x, y);
+  return hipGetLastError();
+}
+
+// Columns per wave.  Measured on the 3 x 20 workload (3600 initial conditions x 100 steps, forward sweep, one lease): 4 columns
+// (15 waves, 128 VGPRs, 63 spills) 58.9 ms, 5 columns (12 waves, 168 VGPRs) 48.4 ms, 6 columns (10 waves, 59 spills) 62.9 ms,
+// 8 columns (8 waves, 234 VGPRs, no spills) 53.4 ms; the general column kernel of qd_device.h 73.1 ms.  Five columns per wave cover
+// N <= 60, eight the rest; only these two are built.
+#define QD_COL_DISPATCH(S, FN, ...)                                                    \
+  do {                                                                                 \
+    if ((S).Q == 2) return (S).N <= 60 ? FN<2, 5>(__VA_ARGS__) : FN<2, 8>(__VA_ARGS__); \
+    if ((S).Q == 3) return (S).N <= 60 ? FN<3, 5>(__VA_ARGS__) : FN<3, 8>(__VA_ARGS__); \
+    return hipErrorInvalidValue;                                                       \
+  } while (0)
 
 }  // namespace qd

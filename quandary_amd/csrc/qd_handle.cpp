@@ -977,6 +977,16 @@ int qd_handle::arm_slices(qd::SweepArgs& a, int nb, int which) {
   return QD_OK;
 }
 
+// the sweep kernel of a plan, forward or adjoint: each lean family picks its instantiation once for both directions
+static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool adjoint, const TuneOpts& opts, hipStream_t st) {
+  switch (plan.family) {
+    case Family::F32: return launch_sweep_f32(a, adjoint, opts, st);
+    case Family::Slot: return launch_sweep_lean64(a, adjoint, opts, st);
+    case Family::Col: return launch_sweep_col(a, adjoint, st);
+    default: return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);  // General and Global: the variant says which
+  }
+}
+
 int qd_handle::forward_dev(const double* dx0, int nb, bool store, const DevTarget* tgp, double* energy) {
   int r;
   if ((r = forward_launch(dx0, nb, store, tgp))) return r;
@@ -1024,12 +1034,7 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   if (a.ztraj) ztraj_fmt = plan.stage_layout();
   take_kernel(0);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 0))) return r;
-  switch (plan.family) {
-    case Family::F32: QD_HIP(launch_forward_f32(a, opts, stream)); break;
-    case Family::Slot: QD_HIP(launch_forward_lean64(a, opts, stream)); break;
-    case Family::Col: QD_HIP(launch_forward_col(a, stream)); break;
-    default: QD_HIP(launch_forward(a, plan.cfg, stream));  // General and Global: the variant says which
-  }
+  QD_HIP(launch_sweep(a, plan, false, opts, stream));
   last_kernel[0] = take_kernel(0);
   QD_HIP(hipEventRecord(ev1, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(h_sched.p, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
@@ -1220,12 +1225,7 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   QD_HIP(hipEventRecord(ev2, stream));
   take_kernel(1);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 1))) return r;
-  switch (plan.family) {
-    case Family::F32: QD_HIP(launch_adjoint_f32(a, opts, stream)); break;
-    case Family::Slot: QD_HIP(launch_adjoint_lean64(a, opts, stream)); break;
-    case Family::Col: QD_HIP(launch_adjoint_col(a, stream)); break;
-    default: QD_HIP(launch_adjoint(a, plan.cfg, stream));  // General and Global: the variant says which
-  }
+  QD_HIP(launch_sweep(a, plan, true, opts, stream));
   last_kernel[1] = take_kernel(1);
   QD_HIP(hipEventRecord(ev3, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));

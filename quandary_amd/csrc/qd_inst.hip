@@ -20,12 +20,6 @@ namespace qd {
 constexpr bool kQubit = (QD_B == 1);
 constexpr bool kDense = (QD_B == 2);  // user-supplied dense Hamiltonians (DenseStencil)
 constexpr bool kLind = (QD_L != 0);
-template <typename K>
-static hipError_t set_lds(K kern, size_t bytes) {
-  if (bytes > 48 * 1024)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return hipSuccess;
-}
 
 // Sweeps of the global-memory kernels (qd_big.h).  One workgroup per initial condition: a plain launch.  Teams: the grid is
 // padded to whole rounds of the 8 XCDs (the members of a team share an XCD), the team barriers spin, so the launch is cooperative -

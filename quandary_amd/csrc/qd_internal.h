@@ -191,6 +191,17 @@ inline bool plain_sweep(const SweepArgs& a, const LaunchCfg& cfg, int adjoint) {
   return !(cfg.noplain & (adjoint ? 2 : 1)) && (cfg.var == 0 || cfg.var == 1) && !cfg.gmres && !a.stepper_ee && !(a.gamma_penalty > 1e-13) && !(a.gamma_dpdm > 1e-13 && !a.S.lindblad);
 }
 
+// compute units of the current device, asked once (qd_kernels.hip)
+int cu_count();
+// Dynamic LDS of a kernel: the attribute a launch with more than 48 KiB needs.  (The lean column kernels of qd_col.h are always above:
+// ColLean::lds_bytes(N) >= 2 KiB per column, at least 66 KiB for the N >= 33 that collean_available admits.)
+template <typename K>
+hipError_t set_lds(K kern, size_t bytes) {
+  if (bytes > 48 * 1024)
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  return hipSuccess;
+}
+
 // kernel launch wrappers implemented in qd_kernels.hip; all return hipError_t
 hipError_t launch_controls(const DevCtlDesc& d, const double* params, const double* times, const double* hs, int nrows,
                            double* table, int cs, hipStream_t st);
@@ -212,21 +223,20 @@ hipError_t launch_reduce_coeff(const double* coeff, int nb, int ncol, double* su
 hipError_t launch_grad(const DevCtlDesc& d, const double* params, const double* table, int cs, int nsub, const double* coeffsum,
                        const double* etable, int nstep, double ebar, double* grad, int ndesign, hipStream_t st);
 // fp32-mixed sweeps of all-qubit Lindblad systems (qd_q32.hip); the trajectory is [nsub+1][nb][dim] float2
-hipError_t launch_forward_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
-hipError_t launch_adjoint_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
+// (one entry point per lean family for both sweeps, adjoint = 0 forward / 1 adjoint: the adjoint kernel reads the primal stages in the
+// element order the forward kernel of the SAME instantiation wrote, so the instantiation is chosen once, whatever the direction)
+hipError_t launch_sweep_f32(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
                             hipStream_t st);
 // the same lean slot kernel instantiated in fp64: Neumann sweeps of the 2^5 Lindblad system (QD_PRECISION_F64)
 bool lean64_available(const DevSys& S, const TuneOpts& o);
-hipError_t launch_forward_lean64(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
-hipError_t launch_adjoint_lean64(const SweepArgs& a, const TuneOpts& o, hipStream_t st);
+hipError_t launch_sweep_lean64(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
 // lean column kernels (qd_col.hip): Lindblad Neumann sweeps of density matrices with 33..64 rows and runtime level counts
 bool collean_available(const DevSys& S, const TuneOpts& o);
 int col_slices(int nb, int ntime, const TuneOpts& o);  // time slices of a lean column sweep (1 = none)
 size_t col_krylov_doubles(int nb, int nslice);  // size of SweepArgs::kry for the Krylov solver of the lean column kernels
-hipError_t launch_forward_col(const SweepArgs& a, hipStream_t st);
-hipError_t launch_adjoint_col(const SweepArgs& a, hipStream_t st);
+hipError_t launch_sweep_col(const SweepArgs& a, bool adjoint, hipStream_t st);
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false);
 size_t krylov_doubles(const DevSys& S, int nb);

@@ -442,6 +442,17 @@ static const VarInfo kVar[NVARIANTS] = {var_info<0>(), var_info<1>(),  var_info<
                                         var_info<12>(), var_info<13>(), var_info<14>(), var_info<15>(), var_info<16>(), var_info<17>()};
 int variant_max_block(int var) { return (var >= 0 && var < NVARIANTS) ? kVar[var].maxb : 0; }
 
+int cu_count() {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
+    if (ncu <= 0) ncu = 256;
+  }
+  return ncu;
+}
+
 void big_team(const DevSys& S, int nb, const TuneOpts& o, int& team, int& spread);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres) {
   LaunchCfg c{};
@@ -523,13 +534,7 @@ LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmre
 // CU is what the register budget of these kernels allows for sure; the cooperative launch checks it).  Members dealt over all XCDs
 // by default.  the options big_team / big_spread override (tests, measurements: profiles/big_probe.py).
 void big_team(const DevSys& S, int nb, const TuneOpts& o, int& team, int& spread) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
+  const int ncu = cu_count();
   spread = o.big_spread >= 0 ? o.big_spread != 0 : 1;
   const int gmax = spread ? BIG_TEAM_MAX : 32;
   const int slots = spread ? nb : (nb + 7) / 8 * 8;

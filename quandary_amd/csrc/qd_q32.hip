@@ -1489,35 +1489,21 @@ __global__ void __launch_bounds__(64) k_apply_mfma32(const DevSys S, const doubl
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-template <typename K>
-static hipError_t set_lds32(K kern, size_t bytes) {
-  if (bytes > 48 * 1024)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return hipSuccess;
-}
-
 template <typename R>
 static const char* type_name() { return sizeof(R) == 4 ? "float" : "double"; }  // (note_kernel)
 
+// one sweep kernel, forward or adjoint, of the instantiation <Q, SB, R, GM, HJ>: the two are a pair (the adjoint kernel reads the primal
+// stages as the forward kernel of the same instantiation stored them), so whoever picks an instantiation picks it for both directions
 template <int Q, int SB, typename R, bool GM = false, bool HJ = false>
-static hipError_t go_fwd(const SweepArgs& a, hipStream_t st) {
+static hipError_t go_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   constexpr int nt = Q32<Q, SB, R>::NT;
   const size_t lds = Team32<Q, SB, R, GM, HJ>::lds_bytes();
-  auto kf = k_forward_q32<Q, SB, R, GM, HJ>;
-  hipError_t e = set_lds32(kf, lds);
+  // (the forward kernel named first: the compiler emits the kernels in the order they are first named, and its code for two of them
+  //  has been seen to depend on that order - profiles/HISTORY.md, "One launcher for both directions")
+  auto kf = !adjoint ? k_forward_q32<Q, SB, R, GM, HJ> : k_adjoint_q32<Q, SB, R, GM, HJ>;
+  hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
-  note_kernel(0, "k_forward_q32", Q, SB, type_name<R>(), GM, HJ);
-  hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
-  return hipGetLastError();
-}
-template <int Q, int SB, typename R, bool GM = false, bool HJ = false>
-static hipError_t go_adj(const SweepArgs& a, hipStream_t st) {
-  constexpr int nt = Q32<Q, SB, R>::NT;
-  const size_t lds = Team32<Q, SB, R, GM, HJ>::lds_bytes();
-  auto kf = k_adjoint_q32<Q, SB, R, GM, HJ>;
-  hipError_t e = set_lds32(kf, lds);
-  if (e != hipSuccess) return e;
-  note_kernel(1, "k_adjoint_q32", Q, SB, type_name<R>(), GM, HJ);
+  note_kernel(adjoint ? 1 : 0, adjoint ? "k_adjoint_q32" : "k_forward_q32", Q, SB, type_name<R>(), GM, HJ);
   hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
   return hipGetLastError();
 }
@@ -1526,53 +1512,39 @@ static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const do
   constexpr int nt = Q32<Q, SB, R>::NT;
   const size_t lds = Team32<Q, SB, R, false, HJ>::lds_bytes();
   auto kf = k_apply_q32<Q, SB, R, HJ>;
-  hipError_t e = set_lds32(kf, lds);
+  hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
   note_kernel(2, "k_apply_q32", Q, SB, type_name<R>(), HJ);
   hipLaunchKernelGGL(kf, dim3(nb), dim3(nt), lds, st, S, ctlrow, tr, x, y, nrep);
   return hipGetLastError();
 }
 
-// 2^5 system, batches of at most one state per CU: 512 threads x 2 elements (see lean64_sb below; the same option)
-static bool small_batch_sb1(const SweepArgs& a, const TuneOpts& o) {
-  if (o.lean64_sb == 1 || o.lean64_sb == 2) return o.lean64_sb == 1;
-  return a.nb <= 256;
+// Elements per thread of the uncoupled 2^5 kernels, as a power of two, in both precisions.  Small batches (at most one state per CU: the
+// shards of a multi-GPU run, BASELINE config 5 on 8 GPUs) run two elements per thread on 512 threads - two waves per SIMD hide part of
+// the latency one 256-thread group per CU leaves exposed: 128 states x 1000 steps, fp64 gradient, one lease: 16.1 -> 15.0 ms (forward
+// 5.5 -> 5.3).  Larger batches keep two 256-thread groups per CU, four elements per thread; so do the Krylov kernels (the only form built).
+static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
+  if (a.use_gmres) return 2;
+  if (o.lean64_sb == 1 || o.lean64_sb == 2) return o.lean64_sb;
+  return a.nb <= 256 ? 1 : 2;
 }
 
-hipError_t launch_forward_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st) {
+hipError_t launch_sweep_f32(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
   if (a.S.hasJ) {  // [r6] dipole-dipole coupling: the coupled stencils in fp32 (stationary iterations only)
     if (a.use_gmres) return hipErrorInvalidValue;
-    if (a.S.Q == 5) return go_fwd<5, 1, float, false, true>(a, st);
-    if (a.S.Q == 4) return go_fwd<4, 0, float, false, true>(a, st);
+    if (a.S.Q == 5) return go_sweep<5, 1, float, false, true>(a, adjoint, st);
+    if (a.S.Q == 4) return go_sweep<4, 0, float, false, true>(a, adjoint, st);
     return hipErrorInvalidValue;
   }
   if (a.use_gmres) {  // Krylov basis in global memory as float2, Hessenberg problem in fp64
-    if (a.S.Q == 5) return go_fwd<5, 2, float, true>(a, st);
-    if (a.S.Q == 4) return go_fwd<4, 0, float, true>(a, st);
-    if (a.S.Q == 3) return go_fwd<3, 0, float, true>(a, st);
+    if (a.S.Q == 5) return go_sweep<5, 2, float, true>(a, adjoint, st);
+    if (a.S.Q == 4) return go_sweep<4, 0, float, true>(a, adjoint, st);
+    if (a.S.Q == 3) return go_sweep<3, 0, float, true>(a, adjoint, st);
     return hipErrorInvalidValue;
   }
-  if (a.S.Q == 5) return small_batch_sb1(a, o) ? go_fwd<5, 1, float>(a, st) : go_fwd<5, 2, float>(a, st);
-  if (a.S.Q == 4) return go_fwd<4, 0, float>(a, st);
-  if (a.S.Q == 3) return go_fwd<3, 0, float>(a, st);  // [r3] 2x2x2 (BASELINE config 2): one wave per initial condition
-  return hipErrorInvalidValue;
-}
-hipError_t launch_adjoint_f32(const SweepArgs& a, const TuneOpts& o, hipStream_t st) {
-  if (a.S.hasJ) {
-    if (a.use_gmres) return hipErrorInvalidValue;
-    if (a.S.Q == 5) return go_adj<5, 1, float, false, true>(a, st);
-    if (a.S.Q == 4) return go_adj<4, 0, float, false, true>(a, st);
-    return hipErrorInvalidValue;
-  }
-  if (a.use_gmres) {
-    if (a.S.Q == 5) return go_adj<5, 2, float, true>(a, st);
-    if (a.S.Q == 4) return go_adj<4, 0, float, true>(a, st);
-    if (a.S.Q == 3) return go_adj<3, 0, float, true>(a, st);
-    return hipErrorInvalidValue;
-  }
-  if (a.S.Q == 5) return small_batch_sb1(a, o) ? go_adj<5, 1, float>(a, st) : go_adj<5, 2, float>(a, st);
-  if (a.S.Q == 4) return go_adj<4, 0, float>(a, st);
-  if (a.S.Q == 3) return go_adj<3, 0, float>(a, st);
+  if (a.S.Q == 5) return lean64_sb(a, o) == 1 ? go_sweep<5, 1, float>(a, adjoint, st) : go_sweep<5, 2, float>(a, adjoint, st);
+  if (a.S.Q == 4) return go_sweep<4, 0, float>(a, adjoint, st);
+  if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);  // [r3] 2x2x2 (BASELINE config 2): one wave per initial condition
   return hipErrorInvalidValue;
 }
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
@@ -1604,28 +1576,13 @@ bool lean64_available(const DevSys& S, const TuneOpts& o) {
     if (S.n[k] != 2 || S.ness[k] != 2) return false;
   return !o.no_lean64;
 }
-// Small batches (at most one state per CU: the shards of a multi-GPU run, BASELINE config 5 on 8 GPUs) run two elements per thread on
-// 512 threads - two waves per SIMD hide part of the latency one 256-thread group per CU leaves exposed: 128 states x 1000 steps,
-// gradient, one lease: 16.1 -> 15.0 ms (forward 5.5 -> 5.3).  Larger batches keep two 256-thread groups per CU.
-static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
-  if (a.use_gmres) return 2;
-  if (o.lean64_sb == 1 || o.lean64_sb == 2) return o.lean64_sb;
-  return a.nb <= 256 ? 1 : 2;
-}
-hipError_t launch_forward_lean64(const SweepArgs& a, const TuneOpts& o, hipStream_t st) {
+hipError_t launch_sweep_lean64(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
   // ([r6] the Krylov solver of these kernels - Team32::kry1 in front of the plain GMRES - also on the coupled stencils)
-  if (a.S.Q == 4 && a.S.hasJ) return a.use_gmres ? go_fwd<4, 0, double, true, true>(a, st) : go_fwd<4, 0, double, false, true>(a, st);
-  if (a.S.Q == 5 && a.S.hasJ) return a.use_gmres ? go_fwd<5, 1, double, true, true>(a, st) : go_fwd<5, 1, double, false, true>(a, st);
-  if (a.S.Q == 4) return a.use_gmres ? go_fwd<4, 0, double, true>(a, st) : go_fwd<4, 0, double>(a, st);  // 2^4: one element per thread, four waves
-  if (lean64_sb(a, o) == 1) return go_fwd<5, 1, double>(a, st);
-  return a.use_gmres ? go_fwd<5, 2, double, true>(a, st) : go_fwd<5, 2, double>(a, st);
-}
-hipError_t launch_adjoint_lean64(const SweepArgs& a, const TuneOpts& o, hipStream_t st) {
-  if (a.S.Q == 4 && a.S.hasJ) return a.use_gmres ? go_adj<4, 0, double, true, true>(a, st) : go_adj<4, 0, double, false, true>(a, st);
-  if (a.S.Q == 5 && a.S.hasJ) return a.use_gmres ? go_adj<5, 1, double, true, true>(a, st) : go_adj<5, 1, double, false, true>(a, st);
-  if (a.S.Q == 4) return a.use_gmres ? go_adj<4, 0, double, true>(a, st) : go_adj<4, 0, double>(a, st);
-  if (lean64_sb(a, o) == 1) return go_adj<5, 1, double>(a, st);
-  return a.use_gmres ? go_adj<5, 2, double, true>(a, st) : go_adj<5, 2, double>(a, st);
+  if (a.S.Q == 4 && a.S.hasJ) return a.use_gmres ? go_sweep<4, 0, double, true, true>(a, adjoint, st) : go_sweep<4, 0, double, false, true>(a, adjoint, st);
+  if (a.S.Q == 5 && a.S.hasJ) return a.use_gmres ? go_sweep<5, 1, double, true, true>(a, adjoint, st) : go_sweep<5, 1, double, false, true>(a, adjoint, st);
+  if (a.S.Q == 4) return a.use_gmres ? go_sweep<4, 0, double, true>(a, adjoint, st) : go_sweep<4, 0, double>(a, adjoint, st);  // 2^4: one element per thread, four waves
+  if (lean64_sb(a, o) == 1) return go_sweep<5, 1, double>(a, adjoint, st);
+  return a.use_gmres ? go_sweep<5, 2, double, true>(a, adjoint, st) : go_sweep<5, 2, double>(a, adjoint, st);
 }
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st) {
   if (S.Q == 4 && S.hasJ) return go_app<4, 0, double, true>(S, ctlrow, transpose, x, y, nb, 1, st);

@@ -163,7 +163,7 @@ def _b(v):
 
 def col_kernels(nlevels, split="0", stepper="IMR", krylov=False):
     """The lean column kernels (qd_col.hip) a Lindblad system of 33 <= N <= 64 rows runs on, as qd_last_kernel names them, per role.
-    The dispatch rule of QD_COL_DISPATCH / col_uslot / go_*_col: five columns per wave up to N = 60, eight above; USLOT where N and the
+    The dispatch rule of QD_COL_DISPATCH / col_uslot / col_sweep / col_apply (qd_col.h): five columns per wave up to N = 60, eight above; USLOT where N and the
     strides of all oscillators but the last are multiples of it; SPLIT from the option neumann_split ("auto" is on for these ladders; the
     operator application takes SPLIT only from neumann_split = 1); SKIP on the one-stage implicit midpoint rule with reltol = 0 (the
     synthetic systems: 1e-20); the Krylov kernels (gmres_split = 0) are always SPLIT and never SKIP."""
