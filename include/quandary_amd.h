@@ -351,6 +351,27 @@ int qd_optim_evalGradF(qd_optim* o, const double* alpha, qd_objective_value* val
  * (forward + adjoint per chunk) wherever the adjoint seeds do not depend on the reduced cost, i.e. everywhere but Schroedinger + Jtrace. */
 int qd_optim_last_chunks(const qd_optim* o);
 
+/* OptimProblem::evalF / evalGradF (src/optimproblem.cpp:224-538) at nset control vectors at once: the trial steps of a line search,
+ * the starts of a multi-start optimisation, finite-difference probes, amplitude scans.  alphas [nset][ndesign]; vals [nset];
+ * grads [nset][ndesign].  Set j's results are those of the single evaluation at alphas[j].  Single rank only (QD_ERR_STATE for an
+ * objective created with nranks > 1); nset < 1 or a null pointer: QD_ERR_INVALID; whatever a single evaluation rejects is rejected
+ * the same way (gradient of pi-pulses or of the spline_amplitude parameterisation: QD_ERR_UNSUPPORTED).
+ * Concurrent path: where a sweep runs on the general kernel family with one workgroup per state (the small Schroedinger and Lindblad
+ * systems that leave most of the device idle), the standard Hamiltonian model, fp64 and a shard that needs no chunking, all sets
+ * share ONE launch per sweep - nset x ninit states, each set reading a control table of its own; one plan is made for all sets, from
+ * the row bound maximised over them.  Sets whose stored trajectories together exceed what one evaluation may allocate (option
+ * traj_budget_mb) are swept in equal groups of the largest size that fits.
+ * Fallback: every other configuration - lean slot, lean column and global-memory kernels, fp32-mixed, user Hamiltonians, teams of
+ * workgroups, chunked shards - is served set by set through the single evaluation: the same results, no speed-up.
+ * After either call the handle holds no stored trajectory (the state and observable getters and the operator-level adjoint sweep return
+ * QD_ERR_STATE) and its control table is stale: the next single evaluation returns what it returned before.  qd_last_mean_applies is
+ * the mean over all sets, qd_last_kernel names the sweep kernels that ran. */
+int qd_optim_evalF_batch(qd_optim* o, const double* alphas, int nset, qd_objective_value* vals);
+int qd_optim_evalGradF_batch(qd_optim* o, const double* alphas, int nset, qd_objective_value* vals, double* grads);
+/* Sets that shared one sweep launch in the last batch call: nset (or the group size) on the concurrent path, 1 where the call was
+ * served set by set. */
+int qd_optim_last_batch_sets(const qd_optim* o);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, initial conditions sharded over the ranks.
  * Replaces the reference's comm_init communicator (src/main.cpp:133-177) and its

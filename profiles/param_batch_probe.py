@@ -1,0 +1,42 @@
+"""Parameter-set batch probe (run on the GPU box): what several control vectors in one sweep launch buy on the small BASELINE
+configurations, whose single sweeps leave most of the device idle (C1: 4 one-wave workgroups, C3: 16).
+For nset in 1, 2, 4, 16, 64, 256: ONE evalGradF_batch / evalF_batch call against the same sets as nset consecutive evalGradF / evalF
+calls - alternating, each twice, in one process on one lease; the comparator is the single-evaluation path as it was.  Wall-clock times
+(the host side is part of what a caller of either form pays).  The control vectors are the workload's own scaled by 1 ... 3.
+usage: param_batch_probe.py [c1 c3 ...] > profiles/param_batch_probe.txt"""
+import os
+import sys
+import time
+
+import numpy as np
+
+_r = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _r)
+from quandary_amd import capi  # noqa: E402
+from quandary_amd.workloads import workload_spec  # noqa: E402
+
+NSETS = (1, 2, 4, 16, 64, 256)
+for which in (sys.argv[1:] or ["c1", "c3"]):
+    for grad in (True, False):
+        sp = workload_spec(which, "gradient" if grad else "simulation", {})
+        h = capi.Handle(sp)
+        o = capi.Optim(h, sp)
+        for nset in NSETS:
+            alphas = np.stack([sp.params0 * (1.0 + 2.0 * j / max(nset - 1, 1)) for j in range(nset)])
+            batch = (lambda: o.evalGradF_batch(alphas)) if grad else (lambda: o.evalF_batch(alphas))
+            single = (lambda: [o.evalGradF(a) for a in alphas]) if grad else (lambda: [o.evalF(a) for a in alphas])
+            batch(), single()  # (allocations, solver latch, tuner)
+            t = {"batch": [], "single": []}
+            for rep in range(2):
+                for tag, fn in (("batch", batch), ("single", single)):
+                    t0 = time.perf_counter()
+                    fn()
+                    t[tag].append((time.perf_counter() - t0) * 1e3)
+                    if tag == "batch":
+                        sets, kern = o.last_batch_sets, h.last_kernel("forward")
+            b, s = min(t["batch"]), min(t["single"])
+            print(which, "grad" if grad else "fwd", "ninit", sp.ninit, "ntime", sp.time.ntime, "nset", nset, "sets_per_launch", sets,
+                  "batch_ms", " ".join("%.2f" % v for v in t["batch"]), "single_ms", " ".join("%.2f" % v for v in t["single"]),
+                  "single_over_batch %.2f" % (s / b), "batch_ms_per_set %.3f" % (b / nset), kern, flush=True)
+        o.close()
+        h.close()

@@ -179,6 +179,7 @@ EXPORTS = [
     "qd_optim_finalize", "qd_optim_adjoint_local", "qd_optim_gradient_local", "qd_optim_evalF", "qd_optim_evalGradF",
     "qd_comm_unique_id", "qd_comm_create", "qd_comm_create_from_file", "qd_comm_create_host", "qd_comm_backend", "qd_comm_destroy", "qd_comm_size", "qd_comm_rank",
     "qd_comm_allreduce", "qd_comm_barrier", "qd_optim_evalF_dist", "qd_optim_evalGradF_dist", "qd_optim_last_chunks", "qd_set_precision", "qd_get_precision", "qd_bench_apply_f32", "qd_get_observables", "qd_set_option",
+    "qd_optim_evalF_batch", "qd_optim_evalGradF_batch", "qd_optim_last_batch_sets",
 ]
 COMM_ID_BYTES = 128
 PRECISION = {"f64": 0, "f32mixed": 1}
@@ -246,6 +247,9 @@ def load_library(path=None):
     lib.qd_optim_gradient_local.argtypes = [vp, c_dp, c_dp, c_dp]
     lib.qd_optim_evalF.argtypes = [vp, c_dp, C.POINTER(qd_objective_value)]
     lib.qd_optim_evalGradF.argtypes = [vp, c_dp, C.POINTER(qd_objective_value), c_dp]
+    lib.qd_optim_evalF_batch.argtypes = [vp, c_dp, C.c_int, C.POINTER(qd_objective_value)]
+    lib.qd_optim_evalGradF_batch.argtypes = [vp, c_dp, C.c_int, C.POINTER(qd_objective_value), c_dp]
+    lib.qd_optim_last_batch_sets.argtypes = [vp]
     lib.qd_comm_unique_id.argtypes = [c_u8p]
     lib.qd_comm_create.argtypes = [c_u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.qd_comm_create_from_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp)]
@@ -548,6 +552,29 @@ class Optim:
     def last_chunks(self):
         """Chunks of the last gradient evaluation (1 = the shard's stored trajectory fitted in HBM)."""
         return self.lib.qd_optim_last_chunks(self._o)
+
+    # several control vectors in one sweep launch (parameter-set batch): alphas [nset, ndesign]
+    def evalF_batch(self, alphas):
+        """qd_optim_evalF_batch: the objective at every row of alphas; a list of dicts, set j as evalF(alphas[j])."""
+        alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1, self.h.ndesign) if self.h.ndesign else np.zeros((len(alphas), 0))
+        nset = alphas.shape[0]
+        vals = (qd_objective_value * max(nset, 1))()
+        _check(self.lib, self.lib.qd_optim_evalF_batch(self._o, dptr(alphas), nset, vals), "qd_optim_evalF_batch")
+        return [vals[j].as_dict() for j in range(nset)]
+
+    def evalGradF_batch(self, alphas):
+        """qd_optim_evalGradF_batch: (list of dicts, gradients [nset, ndesign]), set j as evalGradF(alphas[j])."""
+        alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1, self.h.ndesign) if self.h.ndesign else np.zeros((len(alphas), 0))
+        nset = alphas.shape[0]
+        vals = (qd_objective_value * max(nset, 1))()
+        g = np.zeros((max(nset, 1), max(self.h.ndesign, 1)))
+        _check(self.lib, self.lib.qd_optim_evalGradF_batch(self._o, dptr(alphas), nset, vals, dptr(g)), "qd_optim_evalGradF_batch")
+        return [vals[j].as_dict() for j in range(nset)], np.ascontiguousarray(g[:nset, : self.h.ndesign])
+
+    @property
+    def last_batch_sets(self):
+        """Sets that shared one sweep launch in the last batch call (1 = served set by set through the single evaluation)."""
+        return self.lib.qd_optim_last_batch_sets(self._o)
 
     # multi-GPU: every rank calls with the RCCL communicator (qd_comm*) created for the same rank / nranks
     def evalF_dist(self, comm, alpha):

@@ -2621,7 +2621,18 @@ __device__ __forceinline__ double2 stage_load(const double* ztraj, size_t state,
 
 __device__ __forceinline__ void vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0), expcnt / lgkmcnt untouched
 
-template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false>
+// The control table of a workgroup's state.  One table for all states: A.ctl itself, named at every use as before - a local copy of the
+// pointer changes the register allocation of the existing instantiations (the kernel arguments are re-read from the scalar cache where
+// they are used).  SETS: the table of the state's set.
+template <bool SETS>
+__device__ __forceinline__ const double* sweep_ctl(const SweepArgs& A, int ic0) {
+  if constexpr (SETS) return A.ctl + (size_t)(ic0 / A.nb_set) * A.ctl_set;
+  else return A.ctl;
+}
+
+// SETS: parameter-set batch - the states are sets of A.nb_set, each set with a control table of its own, A.ctl_set doubles apart
+// (qd_optim_evalGradF_batch); everything else is indexed by the state as in any batch.  false: one table, the kernels as they were.
+template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false, bool SETS = false>
 __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward(const SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef Team<Q, LIND, VAR, QUBIT, GM> TM;
@@ -2662,15 +2673,15 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward(const SweepArgs 
   constexpr bool PREFETCH = !TM::V::LEAN;
   constexpr bool XSTASH = TM::V::LEAN;  // explicit staging of the state through L2/HBM instead of compiler spills
   StepC<Q> c, cn;
-  if (PREFETCH) load_step<Q>(A.ctl, cn, jpairs);
+  if (PREFETCH) load_step<Q>(sweep_ctl<SETS>(A, tm.ic0), cn, jpairs);
 
   vm_drain();
   for (int s = 0; s < A.nsub; s++) {
     if (PREFETCH) {
       c = cn;
-      if (s + 1 < A.nsub) load_step<Q>(A.ctl + (size_t)(s + 1) * A.cs, cn, jpairs);  // prefetch the next row
+      if (s + 1 < A.nsub) load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, cn, jpairs);  // prefetch the next row
     } else {
-      load_step<Q>(A.ctl + (size_t)s * A.cs, c, jpairs);
+      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)s * A.cs, c, jpairs);
       scalarize<Q>(c, jpairs);
     }
     c.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)s * S.N * S.N : nullptr;
@@ -2810,7 +2821,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward(const SweepArgs 
 // the reference's backward recomputation of the Schroedinger primal unnecessary - except for explicit
 // Euler, where the recomputed chain differs from the forward states and defines the reference's gradient)
 // ---------------------------------------------------------------------------------------------
-template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false>
+template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false, bool SETS = false>
 __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef Team<Q, LIND, VAR, QUBIT, GM> TM;
@@ -2849,11 +2860,11 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
     load_state(A.nsub, xp);
     for (int s = A.nsub - 1; s >= 0; s--) {
       StepC<Q> c1;
-      load_step<Q>(A.ctl + (size_t)(s + 1) * A.cs, c1, jpairs);  // M(tstop of step s) = row s + 1
+      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, c1, jpairs);  // M(tstop of step s) = row s + 1
       if (TM::V::LEAN) scalarize<Q>(c1, jpairs);
       c1.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)(s + 1) * S.N * S.N : nullptr;
       tm.st.prep(S, tm.L, c1);
-      const double hneg = -A.ctl[(size_t)s * A.cs];
+      const double hneg = -sweep_ctl<SETS>(A, tm.ic0)[(size_t)s * A.cs];
       tm.publish(xp);
       double2 t[EPT];
       tm.template apply_all<false>(S, c1, xp, t);
@@ -2901,7 +2912,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
   };
   if (ZAHEAD && !ee && A.nsub > 0) {
     load_stage(A.nsub - 1, znext);
-    load_step<Q>(A.ctl + (size_t)(A.nsub - 1) * A.cs, cn, jpairs);
+    load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(A.nsub - 1) * A.cs, cn, jpairs);
   }
 
   vm_drain();
@@ -2990,10 +3001,10 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
       for (int j = 0; j < (ZAHEAD ? EPT : 0); j++) znow[j] = znext[j];
       if (s > 0) {
         load_stage(s - 1, znext);
-        load_step<Q>(A.ctl + (size_t)(s - 1) * A.cs, cn, jpairs);
+        load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s - 1) * A.cs, cn, jpairs);
       }
     } else {
-      load_step<Q>(A.ctl + (size_t)s * A.cs, c, jpairs);
+      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)s * A.cs, c, jpairs);
     }
     if (TM::V::LEAN) scalarize<Q>(c, jpairs);
     c.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)s * S.N * S.N : nullptr;
@@ -3023,7 +3034,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
         }
       store_coeffs();
       StepC<Q> c1;
-      load_step<Q>(A.ctl + (size_t)(s + 1) * A.cs, c1, jpairs);
+      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, c1, jpairs);
       c1.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)(s + 1) * S.N * S.N : nullptr;
       tm.st.prep(S, tm.L, c1);
       tm.publish(xb);

@@ -71,6 +71,10 @@ extern "C" void qd_destroy(qd_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
+  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad}) b->release();
+  h->h_bparams.release();
+  h->h_betable.release();
+  h->h_bgrad.release();
   for (DBuf* b : {&h->d_params, &h->d_tbar, &h->d_tred, &h->d_sched_t, &h->d_sched_h, &h->d_etimes, &h->d_ezero, &h->d_table, &h->d_etable, &h->d_onerow,
                   &h->d_onetime, &h->d_tstates, &h->d_purity, &h->d_x0, &h->d_xT, &h->d_traj, &h->d_ztraj, &h->d_res,
                   &h->d_xbar, &h->d_jbar, &h->d_coeff, &h->d_coeffsum, &h->d_grad, &h->d_y, &h->d_sched, &h->d_stash, &h->d_kry, &h->d_ecoef, &h->d_edig, &h->d_work, &h->d_g0, &h->d_hcr, &h->d_hci, &h->d_gtab, &h->d_gone})
@@ -478,6 +482,74 @@ double qd_handle::energy_penalty_host() const {
   return e;
 }
 
+// the same sum over the energy-penalty table of one set of a parameter-set batch
+double qd_handle::batch_energy_host(int set) const {
+  double e = 0.0;
+  for (size_t n = 0; n < etimes.size(); n++) {
+    double pen = 0.0;
+    const double* row = h_betable.p + (size_t)set * batch_etable_set() + n * cs;
+    for (int k = 0; k < S.Q; k++) pen += (row[2 + k] * row[2 + k] + row[2 + S.Q + k] * row[2 + S.Q + k]) / tg.ntime;
+    e += pen;
+  }
+  return e;
+}
+
+// Parameter-set batch: step tables [nset][rows][cs] and energy-penalty tables [nset][ntime][cs] of all sets in one launch, and the row
+// bound every solver gate of the batch looks at: the maximum over the sets (one plan, one solver, for all of them).  The handle's own
+// parameters and tables are not touched; `params` (what the bounds read) is restored before returning.
+int qd_handle::batch_begin(const double* alphas, int nset) {
+  QD_HIP(qd::use_device(device));
+  int r;
+  const size_t np = (size_t)nset * ndesign;
+  if ((r = d_bparams.ensure(np)) || (r = h_bparams.ensure(np)) || (r = d_btable.ensure((size_t)nset * batch_ctl_set())) ||
+      (r = d_betable.ensure((size_t)nset * batch_etable_set())) || (r = h_betable.ensure((size_t)nset * batch_etable_set())))
+    return r;
+  if (np) {
+    std::memcpy(h_bparams.p, alphas, sizeof(double) * np);
+    QD_HIP(hipMemcpyAsync(d_bparams.p, h_bparams.p, sizeof(double) * np, hipMemcpyHostToDevice, stream));
+  }
+  QD_HIP(launch_controls_sets(dctl, d_bparams.p, ndesign, nset, d_sched_t.p, d_sched_h.p, (int)sched_t.size(), d_btable.p, d_etimes.p,
+                              d_ezero.p, (int)etimes.size(), d_betable.p, cs, nullptr, stream));
+  // asynchronous: complete at the stream synchronisation that ends the first sweep
+  QD_HIP(hipMemcpyAsync(h_betable.p, d_betable.p, sizeof(double) * nset * batch_etable_set(), hipMemcpyDeviceToHost, stream));
+  const std::vector<double> keep = params;
+  batch_bound = RowBound{0.0, 0.0, 0.0};
+  for (int j = 0; j < nset; j++) {
+    if (ndesign) std::memcpy(params.data(), alphas + (size_t)j * ndesign, sizeof(double) * ndesign);
+    double dg, of;
+    row_bounds(&dg, &of);
+    batch_bound.diag = std::max(batch_bound.diag, dg);
+    batch_bound.off = std::max(batch_bound.off, of);
+  }
+  params = keep;
+  for (double hh : sched_h) batch_bound.amax = std::max(batch_bound.amax, fabs(hh) / 2.0);
+  params_set = true;  // (the gates have controls to look at)
+  traj_valid = false;
+  return QD_OK;
+}
+
+void qd_handle::batch_end() {
+  sets = 0;
+  batch_first = 0;
+  traj_valid = false;
+  params_dirty = true;  // (the next ordinary sweep evaluates its own table again)
+}
+
+int qd_handle::batch_gradient(double ebar, int nsets, double* grads) {
+  QD_HIP(qd::use_device(device));
+  if (ndesign == 0) return QD_OK;
+  int r;
+  const size_t n = (size_t)nsets * ndesign;
+  if ((r = d_bgrad.ensure(n)) || (r = h_bgrad.ensure(n))) return r;
+  const int nsub_flag = sol.stepper == QD_STEPPER_EE ? -nsub : nsub;
+  QD_HIP(launch_grad_sets(dctl, d_bparams.p + (size_t)batch_first * ndesign, batch_table(), batch_ctl_set(), cs, nsub_flag, d_coeffsum.p,
+                          d_betable.p + (size_t)batch_first * batch_etable_set(), batch_etable_set(), tg.ntime, ebar, d_bgrad.p, ndesign, nsets, stream));
+  QD_HIP(hipMemcpyAsync(h_bgrad.p, d_bgrad.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
+  QD_HIP(hipStreamSynchronize(stream));
+  std::memcpy(grads, h_bgrad.p, sizeof(double) * n);
+  return QD_OK;
+}
+
 extern "C" int qd_eval_controls(qd_handle* h, const double* times, int nt, double* pq) {
   if (!h || !times || !pq || nt < 0) return fail(QD_ERR_INVALID, "qd_eval_controls: bad argument");
   QD_HIP(qd::use_device(h->device));
@@ -820,8 +892,12 @@ Family qd_handle::apply_family(const LaunchCfg& cfg) const { return pick_family(
 SweepPlan qd_handle::plan_sweep(int nb, bool adjoint) const {
   SweepPlan p{};
   RowBound b{0.0, 0.0, 0.0};
-  row_bounds(&b.diag, &b.off);
-  for (double hh : sched_h) b.amax = std::max(b.amax, fabs(hh) / 2.0);
+  if (sets) {
+    b = batch_bound;  // parameter-set batch: the maximum over the sets, nb = the states of ONE set
+  } else {
+    row_bounds(&b.diag, &b.off);
+    for (double hh : sched_h) b.amax = std::max(b.amax, fabs(hh) / 2.0);
+  }
   const bool ee = sol.stepper == QD_STEPPER_EE, f32 = precision == QD_PRECISION_F32MIXED;
   LaunchCfg cfg = pick_config(S, nb, opts, sol.linsolve == QD_LINSOLVE_GMRES);
   p.neumann_split = neumann_split_on(b);
@@ -855,7 +931,7 @@ SweepPlan qd_handle::plan_sweep(int nb, bool adjoint) const {
   p.need_big = cfg.var == 16;
   // (the fp32-mixed GMRES and the fp64 one of the lean slot kernels always keep their basis in global memory [r6])
   if (cfg.gmres == 2 || (cfg.gmres && (p.family == Family::F32 || p.family == Family::Slot)))
-    p.kry_doubles = col ? col_krylov_doubles(nb, col_slices(nb, tg.ntime, opts)) : krylov_doubles(S, nb);
+    p.kry_doubles = col ? col_krylov_doubles(nb, col_slices(nb, tg.ntime, opts)) : krylov_doubles(S, sets ? nb * sets : nb);
   return p;
 }
 
@@ -898,7 +974,9 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   std::memset(&a, 0, sizeof a);
   a.S = h->S;
   if (tg) a.tg = *tg;
-  a.ctl = h->d_table.p;
+  a.ctl = h->sets ? h->batch_table() : h->d_table.p;
+  a.nb_set = h->sets ? nb / h->sets : 0;
+  a.ctl_set = h->sets ? (unsigned)h->batch_ctl_set() : 0u;
   a.cs = h->cs;
   a.nsub = h->nsub;
   a.nstages = h->nstages;
@@ -938,6 +1016,8 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
+  if (sets && (p.family != Family::General || p.team != 1 || S.dense || nb % sets != 0))
+    return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
   return QD_OK;
@@ -983,7 +1063,9 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
     case Family::F32: return launch_sweep_f32(a, adjoint, opts, st);
     case Family::Slot: return launch_sweep_lean64(a, adjoint, opts, st);
     case Family::Col: return launch_sweep_col(a, adjoint, st);
-    default: return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);  // General and Global: the variant says which
+    default:  // General and Global: the variant says which; nb_set: the instantiations with one control table per set
+      if (a.nb_set) return adjoint ? launch_adjoint_sets(a, plan.cfg, st) : launch_forward_sets(a, plan.cfg, st);
+      return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);
   }
 }
 
@@ -1006,9 +1088,9 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   d_out4 = d_res.p + 2 * (size_t)nb;
   d_napply = reinterpret_cast<unsigned long long*>(d_res.p + 6 * (size_t)nb);
   napply_zeroed = false;
-  if ((r = refresh_tables())) return r;
+  if (!sets && (r = refresh_tables())) return r;  // (a parameter-set batch has its tables from batch_begin)
   traj_valid = false;
-  const SweepPlan plan = plan_sweep(nb, false);
+  const SweepPlan plan = plan_sweep(sets ? nb / sets : nb, false);
   fwd_poly = plan.gated_poly;
   // (the adjoint sweep's plan differs from this one in the carried-over degree only: the same family)
   const bool full = store && (!stages_only || adjoint_reads_states(nb, tgp, &plan));
@@ -1206,8 +1288,8 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   if (has_ampbasis) return fail(QD_ERR_UNSUPPORTED, "qd_adjoint: the spline_amplitude parameterisation has no gradient in the reference (src/oscillator.cpp:350-356)");
   int r;
   const size_t ncol = (size_t)nsub * 2 * S.Q;
-  if ((r = d_coeff.ensure((size_t)nb * ncol)) || (r = d_coeffsum.ensure(ncol))) return r;
-  const SweepPlan plan = plan_sweep(nb, true);
+  if ((r = d_coeff.ensure((size_t)nb * ncol)) || (r = d_coeffsum.ensure((sets ? sets : 1) * ncol))) return r;
+  const SweepPlan plan = plan_sweep(sets ? nb / sets : nb, true);
   if (plan.need_big && (r = ensure_big(nb))) return r;
   if ((r = ensure_wj_weights())) return r;
   const bool have_states = pending_store ? pending_full : traj_full;
@@ -1230,7 +1312,8 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   QD_HIP(hipEventRecord(ev3, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_adj = a.sched != nullptr;
-  QD_HIP(launch_reduce_coeff(d_coeff.p, nb, (int)ncol, d_coeffsum.p, accumulate ? 1 : 0, stream));
+  if (sets) QD_HIP(launch_reduce_coeff_sets(d_coeff.p, nb / sets, (int)ncol, d_coeffsum.p, sets, stream));  // once per set, over its own states
+  else QD_HIP(launch_reduce_coeff(d_coeff.p, nb, (int)ncol, d_coeffsum.p, accumulate ? 1 : 0, stream));
   return QD_OK;
 }
 

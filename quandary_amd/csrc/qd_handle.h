@@ -223,6 +223,22 @@ struct qd_handle {
   // gradient from d_coeffsum (+ energy term ebar); writes host grad[ndesign]
   int gradient_from_coeffs(double ebar, double* grad);
   double energy_penalty_host() const;
+  // ---- parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch, qd_optim.cpp) --------------------------------------
+  // Several control vectors in one sweep launch: the batch of a sweep is `sets` sets of nb / sets states, set j reads the control
+  // table batch_table() + j * batch_ctl_set().  While sets > 0 the sweeps use these tables and leave the handle's own (d_table) alone;
+  // plan_sweep decides from batch_bound, the Gershgorin row bound maximised over all sets of the call.
+  int sets = 0;                    // sets of the sweeps being launched (0 = ordinary sweeps)
+  int batch_first = 0;             // first set of the group being swept (tables of all sets of the call are resident)
+  qd::RowBound batch_bound{};
+  qd::DBuf d_bparams, d_btable, d_betable, d_bgrad;
+  qd::HBuf h_bparams, h_betable, h_bgrad;
+  size_t batch_ctl_set() const { return sched_t.size() * (size_t)cs; }    // rows the step table really has x cs
+  size_t batch_etable_set() const { return etimes.size() * (size_t)cs; }
+  const double* batch_table() const { return d_btable.p + (size_t)batch_first * batch_ctl_set(); }
+  int batch_begin(const double* alphas, int nset);  // tables of all sets in one launch, row bound over all sets
+  void batch_end();                                 // back to ordinary sweeps: stored trajectory invalid, control table stale
+  double batch_energy_host(int set) const;          // energy_penalty_host of one set of the call
+  int batch_gradient(double ebar, int nsets, double* grads);  // k_grad once per set of the group -> host grads [nsets][ndesign]
   const double* res_pen() const { return h_res.p; }
   const double* res_dpdm() const { return h_res.p + last_nb; }
   const double* res_out4() const { return h_res.p + 2 * (size_t)last_nb; }

@@ -2,6 +2,9 @@
 // stencil): compiled with -DQD_Q=<1..5> -DQD_L=<0|1> -DQD_B=<0|1>.  Instantiates the persistent sweep
 // kernels for the kernel variants that make sense for that case and exports plain launch functions
 // for the dispatcher in qd_kernels.hip.
+// With -DQD_SETS=1 (objects of their own, build/qd_sets_*.o): the SETS form of the same sweep kernels - one control table per set of
+// SweepArgs::nb_set states (parameter-set batch, qd_optim_evalGradF_batch) - for the variants with one workgroup per state in LDS and
+// the standard Hamiltonian model; no operator application, no global-memory kernels.
 #include "qd_device.h"
 #include "qd_big.h"
 
@@ -11,6 +14,13 @@
 // (four objects per case: forward / adjoint x Neumann / GMRES kernels compile side by side - the five-oscillator Lindblad
 // case alone took 13 minutes as one translation unit)
 constexpr bool kGmPart = (QD_PART >= 2);
+#ifndef QD_SETS
+#define QD_SETS 0
+#endif
+#if QD_SETS && QD_B == 2
+#error "the SETS kernels are built for the standard Hamiltonian model only (QD_B = 0 | 1)"
+#endif
+constexpr bool kSets = (QD_SETS != 0);
 
 namespace qd {
 
@@ -39,19 +49,20 @@ constexpr bool kLind = (QD_L != 0);
 #if QD_PART == 0 || QD_PART == 2
 template <int VAR>
 static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
+  if constexpr (VAR == 16 && !kSets && variant_built(QD_Q, kLind, QD_B, VAR)) {
     note_kernel(0, "k_forward_big", QD_Q, kLind, kDense, kGmPart);
     return launch_big(reinterpret_cast<const void*>(k_forward_big<QD_Q, kLind, kDense, kGmPart>), a, cfg, st);
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart>;
+    auto kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, false, kSets>;
     bool plain = false;
     if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
       plain = plain_sweep(a, cfg, 0);
-      if (plain) kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+      if (plain) kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, true, kSets>;
     }
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
-    note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
+    if constexpr (kSets) note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain, true);
+    else note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
   } else {
@@ -59,7 +70,7 @@ static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream
   }
 }
 #endif
-#if QD_PART == 0
+#if QD_PART == 0 && !QD_SETS
 template <int VAR>
 static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb,
                            const LaunchCfg& cfg, hipStream_t st) {
@@ -85,7 +96,7 @@ static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose,
 #if QD_PART == 1 || QD_PART == 3
 template <int VAR>
 static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
+  if constexpr (VAR == 16 && !kSets && variant_built(QD_Q, kLind, QD_B, VAR)) {
     if constexpr (!kGmPart) {
       if (a.stepper_ee) {
         note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, false, true);
@@ -95,15 +106,16 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, kGmPart, false);
     return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, kGmPart, false>), a, cfg, st);
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart>;
+    auto kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, false, kSets>;
     bool plain = false;
     if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
       plain = plain_sweep(a, cfg, 1);
-      if (plain) kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+      if (plain) kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, true, kSets>;
     }
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
-    note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
+    if constexpr (kSets) note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain, true);
+    else note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
   } else {
@@ -129,32 +141,45 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     default: return hipErrorInvalidValue;    \
   }
 
+#if QD_SETS
+#define QD_FWD inst_forwardsets_
+#define QD_FWDGM inst_forwardgmsets_
+#define QD_ADJ inst_adjointsets_
+#define QD_ADJGM inst_adjointgmsets_
+#else
+#define QD_FWD inst_forward_
+#define QD_FWDGM inst_forwardgm_
+#define QD_ADJ inst_adjoint_
+#define QD_ADJGM inst_adjointgm_
+#endif
 #if QD_PART == 0
-hipError_t QD_NAME(inst_forwardgm_, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-hipError_t QD_NAME(inst_forward_, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (cfg.gmres) return QD_NAME(inst_forwardgm_, QD_Q, QD_L, QD_B)(a, cfg, st);  // GMRES kernels: another object
+hipError_t QD_NAME(QD_FWDGM, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+hipError_t QD_NAME(QD_FWD, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (cfg.gmres) return QD_NAME(QD_FWDGM, QD_Q, QD_L, QD_B)(a, cfg, st);  // GMRES kernels: another object
   QD_VAR_SWITCH(go_forward, a, cfg, st)
 }
+#if !QD_SETS
 hipError_t QD_NAME(inst_apply_, QD_Q, QD_L, QD_B)(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y,
                                                   int nb, const LaunchCfg& cfg, hipStream_t st) {
   QD_VAR_SWITCH(go_apply, S, ctlrow, transpose, x, y, nb, cfg, st)
 }
+#endif
 #elif QD_PART == 1
-hipError_t QD_NAME(inst_adjointgm_, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-hipError_t QD_NAME(inst_adjoint_, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (cfg.gmres && !(cfg.var == 16 && a.stepper_ee)) return QD_NAME(inst_adjointgm_, QD_Q, QD_L, QD_B)(a, cfg, st);  // (explicit Euler has no linear solve)
+hipError_t QD_NAME(QD_ADJGM, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+hipError_t QD_NAME(QD_ADJ, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (cfg.gmres && !(cfg.var == 16 && a.stepper_ee)) return QD_NAME(QD_ADJGM, QD_Q, QD_L, QD_B)(a, cfg, st);  // (explicit Euler has no linear solve)
   QD_VAR_SWITCH(go_adjoint, a, cfg, st)
 }
 #elif QD_PART == 2
-hipError_t QD_NAME(inst_forwardgm_, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+hipError_t QD_NAME(QD_FWDGM, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   QD_VAR_SWITCH(go_forward, a, cfg, st)
 }
 #else
-hipError_t QD_NAME(inst_adjointgm_, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+hipError_t QD_NAME(QD_ADJGM, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   QD_VAR_SWITCH(go_adjoint, a, cfg, st)
 }
 #endif
-#if QD_B == 0 && QD_PART == 0
+#if QD_B == 0 && QD_PART == 0 && !QD_SETS
 hipError_t QD_NAME(inst_bigtable_, QD_Q, QD_L, QD_B)(const DevSys& S, double* ecoef, unsigned* edig, hipStream_t st) {
   hipLaunchKernelGGL((k_big_table<QD_Q, kLind>), dim3((S.dim + 255) / 256), dim3(256), 0, st, S, reinterpret_cast<double2*>(ecoef),
                      reinterpret_cast<uint2*>(edig));

@@ -106,6 +106,11 @@ struct SweepArgs {
   // penalties (src/timestepper.cpp:256-480)
   double gamma_penalty, penalty_param, gamma_dpdm;
   int leak_on;
+  // parameter-set batch (qd_optim_evalGradF_batch; read by the SETS instantiations of k_forward / k_adjoint only): the nb states are
+  // nb / nb_set sets of nb_set states, state b reads the control table of set b / nb_set at ctl + (b / nb_set) * ctl_set.  (Both sit
+  // in what was padding behind an int: size and field offsets of the struct - which the GMRES kernels of the several-elements-per-
+  // thread variants keep a copy of in scratch - are those of the struct without them.)
+  int nb_set;  // states per set (0 = one table for all states)
   // forward
   const double* x0;  // [nb][2*dim]
   double* xT;        // [nb][2*dim]
@@ -125,6 +130,7 @@ struct SweepArgs {
   // time-sliced scheduling of the lean column kernels (qd_col.hip): nslice slices of whole time steps, tasks drawn from sched[0]
   // (sched = nullptr: one workgroup per initial condition); the adjoint state is carried from slice to slice in `stash`
   int nslice;
+  unsigned ctl_set;  // parameter-set batch: doubles between two sets' tables = (rows of one table) x cs
   unsigned* sched;
   int col_noskip;  // lean column kernels: test the stopping rule in every pass (option col_skip = 0)
   unsigned long long sched_ticks;  // wall_clock64 ticks (100 MHz) a slice may wait for its predecessor before the error word is raised
@@ -212,6 +218,13 @@ hipError_t launch_apply(const DevSys& S, const double* ctlrow, int transpose, co
                         const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+// the same sweeps with one control table per set of a.nb_set states (qd_inst_sets.hip): standard Hamiltonian model, every LDS variant
+hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+// control tables of nset parameter vectors in one launch: params [nset][ndesign] -> table [nset][nrows][cs], table2 [nset][nrows2][cs]
+hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int ndesign, int nset, const double* times, const double* hs, int nrows,
+                                double* table, const double* times2, const double* hs2, int nrows2, double* table2, int cs,
+                                unsigned long long* zero_me, hipStream_t st);
 hipError_t launch_gmat(const DevSys& S, const double* g0, const double* table, int cs, int nrows, double* gtab, hipStream_t st);
 hipError_t launch_objective(const DevSys& S, const DevTarget& tg, const double* x, int nb, double* out4, hipStream_t st);
 hipError_t launch_seed(const DevSys& S, const DevTarget& tg, const double* x, const double* rbar_ibar, int nb, double* xbar,
@@ -222,6 +235,11 @@ hipError_t launch_seed_weights(const double* sums, const double* w, int nb, int 
 hipError_t launch_reduce_coeff(const double* coeff, int nb, int ncol, double* sum, int accumulate, hipStream_t st);
 hipError_t launch_grad(const DevCtlDesc& d, const double* params, const double* table, int cs, int nsub, const double* coeffsum,
                        const double* etable, int nstep, double ebar, double* grad, int ndesign, hipStream_t st);
+// ... once per set, each over its own nb states / with its own parameters and tables (set strides in doubles): coeff [nset][nb][ncol] ->
+// sum [nset][ncol]; grad [nset][ndesign] from params [nset][ndesign], table + set * table_set, etable + set * etable_set
+hipError_t launch_reduce_coeff_sets(const double* coeff, int nb, int ncol, double* sum, int nset, hipStream_t st);
+hipError_t launch_grad_sets(const DevCtlDesc& d, const double* params, const double* table, size_t table_set, int cs, int nsub, const double* coeffsum,
+                            const double* etable, size_t etable_set, int nstep, double ebar, double* grad, int ndesign, int nset, hipStream_t st);
 // fp32-mixed sweeps of all-qubit Lindblad systems (qd_q32.hip); the trajectory is [nsub+1][nb][dim] float2
 // (one entry point per lean family for both sweeps, adjoint = 0 forward / 1 adjoint: the adjoint kernel reads the primal stages in the
 // element order the forward kernel of the SAME instantiation wrote, so the instantiation is chosen once, whatever the direction)

@@ -120,13 +120,18 @@ __device__ inline void eval_control_dev(const DevCtlDesc& d, const double* __res
 }
 
 // Two row sets in one launch (step table + energy-penalty table of one parameter update); `zero_me`
-// (optional) is the RHS-application counter of the sweep that follows.
+// (optional) is the RHS-application counter of the sweep that follows.  grid.y = parameter sets (launch_controls_sets): set j reads
+// params + j * ndesign and writes the tables of its own, table + j * nrows * cs and table2 + j * nrows2 * cs - the set stride is the
+// number of rows a table really has (composite steppers: stages x ntime; explicit Euler: one row more), on the same time grids.
 __global__ void k_controls(const DevCtlDesc d, const double* __restrict__ params, const double* __restrict__ times,
                            const double* __restrict__ hs, int nrows, double* __restrict__ table, const double* __restrict__ times2,
                            const double* __restrict__ hs2, int nrows2, double* __restrict__ table2, int cs,
-                           unsigned long long* __restrict__ zero_me) {
+                           unsigned long long* __restrict__ zero_me, int ndesign) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx == 0 && zero_me) *zero_me = 0ull;
+  if (idx == 0 && blockIdx.y == 0 && zero_me) *zero_me = 0ull;
+  params += (size_t)blockIdx.y * ndesign;
+  table += (size_t)blockIdx.y * nrows * cs;
+  if (table2) table2 += (size_t)blockIdx.y * nrows2 * cs;
   int row = idx / d.Q;
   const int k = idx % d.Q;
   if (row >= nrows + nrows2) return;
@@ -196,10 +201,13 @@ __global__ void k_seed(const DevSys S, const DevTarget tg, const double* __restr
   }
 }
 
-// coeff[nb][ncol] -> sum over the batch in a fixed order (deterministic gradient)
+// coeff[nb][ncol] -> sum over the batch in a fixed order (deterministic gradient); grid.y = parameter sets, each over its own nb
+// states: coeff[set][nb][ncol] -> sum[set][ncol]
 __global__ void k_reduce_coeff(const double* __restrict__ coeff, int nb, int ncol, double* __restrict__ sum, int accumulate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ncol) return;
+  coeff += (size_t)blockIdx.y * nb * ncol;
+  sum += (size_t)blockIdx.y * ncol;
   double s = accumulate ? sum[i] : 0.0;
   for (int b = 0; b < nb; b++) s += coeff[(size_t)b * ncol + i];
   sum[i] = s;
@@ -210,10 +218,18 @@ __global__ void k_reduce_coeff(const double* __restrict__ coeff, int nb, int nco
 //  BSpline0::derivative :245-254, energyPenaltyIntegral_diff timestepper.cpp:458-480)
 __global__ void __launch_bounds__(64) k_grad(const DevCtlDesc d, const double* __restrict__ params, const double* __restrict__ table, int cs, int nsub, int ee,
                                              const double* __restrict__ coeffsum, const double* __restrict__ etable, int nstep,
-                                             double ebar, double* __restrict__ grad, int ndesign) {
+                                             double ebar, double* __restrict__ grad, int ndesign, size_t table_set, size_t etable_set) {
   // one wave per design parameter; lanes stride over the sub-steps, fixed-order wave reduction
   const int idx = blockIdx.x, lane = threadIdx.x;
   if (idx >= ndesign) return;
+  {  // grid.y = parameter sets (launch_grad_sets): parameters, tables, coefficient sums and gradient of the set
+    const size_t set = blockIdx.y;
+    params += set * ndesign;
+    table += set * table_set;
+    coeffsum += set * nsub * 2 * d.Q;
+    etable += set * etable_set;
+    grad += set * ndesign;
+  }
   // locate (oscillator, segment, carrier, spline, part)
   int k = 0;
   while (k < d.Q - 1 && idx >= d.oscs[k].offset + d.oscs[k].nparams) k++;
@@ -670,6 +686,33 @@ static const apply_fn app_tab[3][2][8] = {{QD_ROW8(inst_apply_, 0, 0), QD_ROW8(i
                                           {QD_ROW8(inst_apply_, 0, 1), QD_ROW(inst_apply_, 1, 1)},
                                           {QD_ROW8(inst_apply_, 0, 2), QD_ROW8(inst_apply_, 1, 2)}};
 
+// the SETS form of the same kernels (qd_inst.hip with -DQD_SETS=1): standard Hamiltonian model only, index [qubit][lindblad][Q-1]
+#define QD_DECLS(q, l, b)                                                                        \
+  hipError_t inst_forwardsets_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t); \
+  hipError_t inst_adjointsets_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
+#define QD_DECLS_Q(l, b) QD_DECLS(1, l, b) QD_DECLS(2, l, b) QD_DECLS(3, l, b) QD_DECLS(4, l, b) QD_DECLS(5, l, b)
+QD_DECLS_Q(0, 0) QD_DECLS_Q(1, 0) QD_DECLS_Q(0, 1) QD_DECLS_Q(1, 1)
+QD_DECLS(6, 0, 0) QD_DECLS(7, 0, 0) QD_DECLS(8, 0, 0) QD_DECLS(6, 0, 1) QD_DECLS(7, 0, 1) QD_DECLS(8, 0, 1)
+QD_DECLS(6, 1, 0) QD_DECLS(7, 1, 0) QD_DECLS(8, 1, 0)
+static const sweep_fn fwd_sets_tab[2][2][8] = {{QD_ROW8(inst_forwardsets_, 0, 0), QD_ROW8(inst_forwardsets_, 1, 0)},
+                                               {QD_ROW8(inst_forwardsets_, 0, 1), QD_ROW(inst_forwardsets_, 1, 1)}};
+static const sweep_fn adj_sets_tab[2][2][8] = {{QD_ROW8(inst_adjointsets_, 0, 0), QD_ROW8(inst_adjointsets_, 1, 0)},
+                                               {QD_ROW8(inst_adjointsets_, 0, 1), QD_ROW(inst_adjointsets_, 1, 1)}};
+
+// a.nb states = a.nb / a.nb_set sets; a missing instantiation (dense operator, global-memory kernels) is an error, never another kernel
+hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 1 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
+      !fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
+    return hipErrorInvalidValue;
+  return fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+}
+hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 1 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
+      !adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
+    return hipErrorInvalidValue;
+  return adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+}
+
 hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   if (a.S.Q < 1 || a.S.Q > 8 || !fwd_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
   return fwd_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
@@ -695,7 +738,17 @@ hipError_t launch_controls2(const DevCtlDesc& d, const double* params, const dou
   const int total = (nrows + nrows2) * d.Q;
   if (total == 0 && !zero_me) return hipSuccess;
   hipLaunchKernelGGL(k_controls, dim3((total > 0 ? total + 127 : 128) / 128), dim3(128), 0, st, d, params, times, hs, nrows, table,
-                     times2, hs2, nrows2, table2, cs, zero_me);
+                     times2, hs2, nrows2, table2, cs, zero_me, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int ndesign, int nset, const double* times, const double* hs, int nrows,
+                                double* table, const double* times2, const double* hs2, int nrows2, double* table2, int cs,
+                                unsigned long long* zero_me, hipStream_t st) {
+  const int total = (nrows + nrows2) * d.Q;
+  if (nset < 1 || nset > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_controls, dim3((total > 0 ? total + 127 : 128) / 128, nset), dim3(128), 0, st, d, params, times, hs, nrows, table,
+                     times2, hs2, nrows2, table2, cs, zero_me, ndesign);
   return hipGetLastError();
 }
 
@@ -754,13 +807,30 @@ hipError_t launch_reduce_coeff(const double* coeff, int nb, int ncol, double* su
   return hipGetLastError();
 }
 
+hipError_t launch_reduce_coeff_sets(const double* coeff, int nb, int ncol, double* sum, int nset, hipStream_t st) {
+  if (nset < 1 || nset > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_reduce_coeff, dim3((ncol + 255) / 256, nset), dim3(256), 0, st, coeff, nb, ncol, sum, 0);
+  return hipGetLastError();
+}
+
 hipError_t launch_grad(const DevCtlDesc& d, const double* params, const double* table, int cs, int nsub, const double* coeffsum, const double* etable,
                        int nstep, double ebar, double* grad, int ndesign, hipStream_t st) {
   if (ndesign == 0) return hipSuccess;
   const int ee = nsub < 0;  // negative nsub flags the explicit-Euler gradient time (t_stop)
   const int ns = ee ? -nsub : nsub;
   hipLaunchKernelGGL(k_grad, dim3(ndesign), dim3(64), 0, st, d, params, table, cs, ns, ee, coeffsum, etable, nstep, ebar, grad,
-                     ndesign);
+                     ndesign, (size_t)0, (size_t)0);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_sets(const DevCtlDesc& d, const double* params, const double* table, size_t table_set, int cs, int nsub, const double* coeffsum,
+                            const double* etable, size_t etable_set, int nstep, double ebar, double* grad, int ndesign, int nset, hipStream_t st) {
+  if (ndesign == 0) return hipSuccess;
+  if (nset < 1 || nset > 65535) return hipErrorInvalidValue;
+  const int ee = nsub < 0;
+  const int ns = ee ? -nsub : nsub;
+  hipLaunchKernelGGL(k_grad, dim3(ndesign, nset), dim3(64), 0, st, d, params, table, cs, ns, ee, coeffsum, etable, nstep, ebar, grad,
+                     ndesign, table_set, etable_set);
   return hipGetLastError();
 }
 

@@ -40,6 +40,11 @@ struct qd_optim {
   bool stored = false, forward_done = false;
   int last_chunks = 1;  // chunks of the last gradient evaluation (1 = the shard's trajectory fitted)
   int dist_fits = -1;  // qd_optim_evalGradF_dist: -1 undecided, 1 fused device path, 0 host-staged fallback (decided collectively)
+  // parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch): the local batch replicated once per set of a sweep launch -
+  // initial states, targets, purities, penalty coefficients - and the seeds of all sets
+  DBuf d_bx0, d_btgt, d_bpur, d_bjbar, d_brbib, d_bxbar;
+  int batch_replicas = 0;    // sets the replicas hold
+  int last_batch_sets = 0;   // qd_optim_last_batch_sets
 };
 
 // ---- index helpers (src/util.cpp:150-278) ------------------------------------------------------
@@ -237,6 +242,7 @@ extern "C" void qd_optim_destroy(qd_optim* o) {
   (void)hipSetDevice(o->h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
   for (DBuf* b : {&o->d_x0, &o->d_tgt, &o->d_pur, &o->d_rbib, &o->d_jbar, &o->d_xbar, &o->d_w, &o->d_red}) b->release();
+  for (DBuf* b : {&o->d_bx0, &o->d_btgt, &o->d_bpur, &o->d_bjbar, &o->d_brbib, &o->d_bxbar}) b->release();
   o->h_red.release();
   for (hipEvent_t e : o->evr)
     if (e) (void)hipEventDestroy(e);
@@ -549,9 +555,10 @@ static DevTarget shifted_target(const qd_optim* o, int offset) {
 }
 
 // the seven sums of the last forward sweep, which propagated the local initial conditions [off, off + nc): src/optimproblem.cpp:258-279
-static void add_partial_sums(const qd_optim* o, int off, int nc, double energy, double* partial) {
+// (res0: where the nc states sit in the batch of the sweep - a parameter-set batch sums every set's states apart)
+static void add_partial_sums(const qd_optim* o, int off, int nc, double energy, double* partial, int res0 = 0) {
   const qd_handle* h = o->h;
-  const double *pen = h->res_pen(), *dpdm = h->res_dpdm(), *o4 = h->res_out4();  // pinned, downloaded with the sweep
+  const double *pen = h->res_pen() + res0, *dpdm = h->res_dpdm() + res0, *o4 = h->res_out4() + 4 * (size_t)res0;  // pinned, downloaded with the sweep
   for (int i = 0; i < nc; i++) {
     const double w = o->weights[o->first + off + i];
     partial[QD_SUM_PENALTY] += w * o->pen.gamma_penalty * (o->pen.gamma_penalty > 1e-13 ? pen[i] : 0.0);
@@ -946,3 +953,159 @@ extern "C" int qd_optim_evalGradF_dist(qd_optim* o, qd_comm* c, const double* al
   QD_HIP(hipEventRecord(o->evr[3], h->stream));
   return dist_finish(o, alpha, true, val, grad, allreduce_ms);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Parameter-set batch: evalF / evalGradF at nset control vectors at once (single rank).
+// Concurrent path - the sweep's plan is the general kernel family with one workgroup per state, standard Hamiltonian
+// model, fp64, a shard whose trajectory fits without chunking: ONE launch per sweep over nset x nlocal states, set j
+// reading its own control table (SweepArgs::nb_set / ctl_set, the SETS instantiations of k_forward / k_adjoint).  The
+// local batch is replicated once per set; trajectory, stages, coefficients and results are indexed by the state as in
+// any batch.  Forward all sets, then every set's sums, objective and adjoint seeds from ITS OWN reduced cost
+// (Schroedinger + Jtrace, src/optimproblem.cpp:495-511) through the code of the single evaluation, adjoint all sets,
+// coefficient reduction and k_grad once per set - each set's numbers come out of the same operations in the same order
+// as qd_optim_evalGradF's.  Sets whose trajectories exceed what one evaluation may allocate (trajectory_fits) go in
+// equal groups of the largest size that fits.  Everything else - lean slot / lean column / global-memory families,
+// fp32-mixed, user Hamiltonians, teams, chunked shards - is served set by set through the single evaluation.
+// ---------------------------------------------------------------------------------------------------------------
+static int ensure_replicas(qd_optim* o, int g) {
+  if (g <= o->batch_replicas) return QD_OK;
+  qd_handle* h = o->h;
+  const int nl = o->nlocal;
+  const size_t n2 = (size_t)2 * h->S.dim, ns = (size_t)nl * n2;
+  int r;
+  o->batch_replicas = 0;
+  if ((r = o->d_bx0.ensure(g * ns)) || (r = o->d_bpur.ensure((size_t)g * nl)) || (r = o->d_bjbar.ensure((size_t)g * 3 * nl)) ||
+      (r = o->d_brbib.ensure((size_t)g * 2 * nl)) || (r = o->d_bxbar.ensure(g * ns)) || (o->tg.tstates && (r = o->d_btgt.ensure(g * ns))))
+    return r;
+  for (int j = 0; j < g; j++) {
+    QD_HIP(hipMemcpyAsync(o->d_bx0.p + j * ns, o->d_x0.p, sizeof(double) * ns, hipMemcpyDeviceToDevice, h->stream));
+    QD_HIP(hipMemcpyAsync(o->d_bpur.p + (size_t)j * nl, o->d_pur.p, sizeof(double) * nl, hipMemcpyDeviceToDevice, h->stream));
+    QD_HIP(hipMemcpyAsync(o->d_bjbar.p + (size_t)j * 3 * nl, o->d_jbar.p, sizeof(double) * 3 * nl, hipMemcpyDeviceToDevice, h->stream));
+    if (o->tg.tstates) QD_HIP(hipMemcpyAsync(o->d_btgt.p + j * ns, o->d_tgt.p, sizeof(double) * ns, hipMemcpyDeviceToDevice, h->stream));
+  }
+  o->batch_replicas = g;
+  return QD_OK;
+}
+
+// leaves the handle on ordinary sweeps however the batch call ends
+struct BatchScope {
+  qd_handle* h;
+  bool stages_saved;
+  BatchScope(qd_handle* hh, bool stages) : h(hh), stages_saved(hh->stages_only) { if (stages) h->stages_only = true; }
+  ~BatchScope() {
+    h->stages_only = stages_saved;
+    h->batch_end();
+  }
+};
+
+static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mode, qd_objective_value* vals, double* grads, const char* who) {
+  if (!o || !vals || (grad_mode && !grads) || nset < 1 || (!alphas && o->h->ndesign > 0)) return fail(QD_ERR_INVALID, std::string(who) + ": null argument or nset < 1");
+  if (o->nranks != 1) return fail(QD_ERR_STATE, std::string(who) + ": single-rank entry point (the distributed form takes one control vector per call)");
+  qd_handle* h = o->h;
+  if (grad_mode && h->has_pipulse) return fail(QD_ERR_UNSUPPORTED, "qd_adjoint: derivative of pi-pulses is not implemented in the reference (src/oscillator.cpp:373-378)");
+  if (grad_mode && h->has_ampbasis) return fail(QD_ERR_UNSUPPORTED, "qd_adjoint: the spline_amplitude parameterisation has no gradient in the reference (src/oscillator.cpp:350-356)");
+  QD_HIP(qd::use_device(h->device));
+  const int nl = o->nlocal, nd = h->ndesign;
+  int r, group = 0;
+  o->last_chunks = 1;
+  {
+    PenaltyScope ps(h, o->pen);
+    BatchScope bs(h, grad_mode);
+    if ((r = h->batch_begin(alphas, nset))) return r;
+    // one plan for all sets: the per-set batch size, the row bound maximised over the sets
+    h->sets = nset;
+    const SweepPlan plan = h->plan_sweep(nl, false);
+    bool concurrent = plan.family == Family::General && plan.team == 1 && !h->S.dense && h->precision == QD_PRECISION_F64 && nset <= 65535 &&
+                      h->batch_ctl_set() <= 0xffffffffull;  // (grid.y of the per-set kernels; SweepArgs::ctl_set is 32 bits wide)
+    if (concurrent) {
+      group = nset;
+      if (grad_mode) {  // the stored trajectory and stages of a group: within what a single evaluation may allocate
+        h->sets = 1;
+        int lo = trajectory_fits(h, nl, &o->tg) ? 1 : 0, hi = nset + 1;  // lo sets fit, hi do not
+        while (lo > 0 && hi - lo > 1) {
+          const int mid = lo + (hi - lo) / 2;
+          if (trajectory_fits(h, mid * nl, &o->tg)) lo = mid;
+          else hi = mid;
+        }
+        const int ngroups = lo > 0 ? (nset + lo - 1) / lo : 0;
+        group = lo > 0 ? (nset + ngroups - 1) / ngroups : 0;  // equal groups of the largest size that fits
+      }
+      concurrent = group > 0;  // (a shard that needs chunking for one set already: set by set)
+    }
+    if (concurrent) {
+      DevTarget tgb = o->tg;
+      std::vector<double> sums((size_t)group * QD_NSUMS), rbib((size_t)group * 2 * nl);
+      double applies = 0.0, fwd_ms = 0.0, adj_ms = 0.0;
+      for (int j0 = 0; j0 < nset; j0 += group) {
+        const int g = std::min(group, nset - j0), nb = g * nl;
+        h->sets = g;
+        h->batch_first = j0;
+        if ((r = ensure_replicas(o, g))) return r;
+        tgb.tstates = o->tg.tstates ? o->d_btgt.p : nullptr;
+        tgb.purity = o->d_bpur.p;
+        if ((r = h->forward_dev(o->d_bx0.p, nb, grad_mode, &tgb, nullptr))) return r;
+        applies += h->last_mean_applies * g;
+        fwd_ms += h->last_fwd_ms;
+        for (int s = 0; s < g; s++) {  // every set's sums over its own states, as the single evaluation forms them
+          double* sm = sums.data() + (size_t)s * QD_NSUMS;
+          const double* alpha = alphas + (size_t)(j0 + s) * nd;
+          for (int i = 0; i < QD_NSUMS; i++) sm[i] = 0.0;
+          add_partial_sums(o, 0, nl, h->batch_energy_host(j0 + s), sm, s * nl);
+          if ((r = qd_optim_finalize(o, alpha, sm, vals + j0 + s))) return r;
+          double rb, ib;  // adjoint seeds from the set's own cost (src/optimproblem.cpp:433-436, :508-511)
+          finalize_J_diff(o, sm[QD_SUM_COST_RE], sm[QD_SUM_COST_IM], &rb, &ib);
+          for (int i = 0; i < nl; i++) {
+            const double w = o->weights[o->first + i];
+            rbib[2 * ((size_t)s * nl + i)] = w * rb;
+            rbib[2 * ((size_t)s * nl + i) + 1] = w * ib;
+          }
+        }
+        if (!grad_mode) continue;
+        QD_HIP(hipMemcpyAsync(o->d_brbib.p, rbib.data(), sizeof(double) * 2 * nb, hipMemcpyHostToDevice, h->stream));
+        QD_HIP(launch_seed(h->S, tgb, h->d_xT.p, o->d_brbib.p, nb, o->d_bxbar.p, h->stream));
+        if ((r = h->adjoint_dev(o->d_bxbar.p, o->d_bjbar.p, nb, &tgb, false))) return r;  // (synchronises: rbib may be rewritten)
+        adj_ms += h->last_adj_ms;
+        if ((r = h->batch_gradient(o->ebar, g, grads + (size_t)j0 * nd))) return r;
+        for (int s = 0; s < g; s++) {  // regularisation terms on the host, per set (src/optimproblem.cpp:356-372)
+          const double* alpha = alphas + (size_t)(j0 + s) * nd;
+          double* grad = grads + (size_t)(j0 + s) * nd;
+          for (int i = 0; i < nd; i++) grad[i] += o->gamma_tik * (alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]));
+          control_variation(h, alpha, grad, 0.5 * o->gamma_var);
+        }
+      }
+      h->last_mean_applies = applies / nset;
+      h->last_fwd_ms = fwd_ms;
+      if (grad_mode) h->last_adj_ms = adj_ms;
+    }
+  }  // (ordinary sweeps from here on)
+  o->stored = false;
+  o->forward_done = false;
+  if (group > 0) {
+    o->last_batch_sets = group;
+    return QD_OK;
+  }
+  // fallback: set by set through the single evaluation - the same results, no launch shared
+  double applies = 0.0;
+  for (int j = 0; j < nset; j++) {
+    const double* alpha = alphas + (size_t)j * nd;
+    r = grad_mode ? qd_optim_evalGradF(o, alpha, vals + j, grads + (size_t)j * nd) : qd_optim_evalF(o, alpha, vals + j);
+    if (r) return r;
+    applies += h->last_mean_applies;
+  }
+  h->last_mean_applies = applies / nset;
+  h->batch_end();  // (the same state after the call on both paths: no stored trajectory, control table stale)
+  o->stored = false;
+  o->forward_done = false;
+  o->last_batch_sets = 1;
+  return QD_OK;
+}
+
+extern "C" int qd_optim_evalF_batch(qd_optim* o, const double* alphas, int nset, qd_objective_value* vals) {
+  return batch_eval(o, alphas, nset, false, vals, nullptr, "qd_optim_evalF_batch");
+}
+
+extern "C" int qd_optim_evalGradF_batch(qd_optim* o, const double* alphas, int nset, qd_objective_value* vals, double* grads) {
+  return batch_eval(o, alphas, nset, true, vals, grads, "qd_optim_evalGradF_batch");
+}
+
+extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_batch_sets : QD_ERR_INVALID; }
