@@ -361,8 +361,14 @@ int qd_optim_last_chunks(const qd_optim* o);
  * share ONE launch per sweep - nset x ninit states, each set reading a control table of its own; one plan is made for all sets, from
  * the row bound maximised over them.  Sets whose stored trajectories together exceed what one evaluation may allocate (option
  * traj_budget_mb) are swept in equal groups of the largest size that fits.
- * Fallback: every other configuration - lean slot, lean column and global-memory kernels, fp32-mixed, user Hamiltonians, teams of
- * workgroups, chunked shards - is served set by set through the single evaluation: the same results, no speed-up.
+ * Option batch_lean (qd_set_option; 0 = default, 1 = on): the concurrent path also serves the lean slot family (2^4 / 2^5 all-qubit
+ * Lindblad systems, fp64) and the fp32-mixed sweeps, wherever the kernel's linear solver is a stationary iteration - a neumann request,
+ * or a gmres request served by the stand-in; their Krylov kernels (gmres_split = 0) keep going set by set.  The uncoupled 2^5 system
+ * picks one or two elements per thread from the states of the whole launch, nset x ninit, so a batch may run another instantiation
+ * than the single evaluation of the same shard (option lean64_sb pins it for both).  Off by default (profiles/param_batch_probe.txt has what it buys).
+ * Fallback: every other configuration - lean column and global-memory kernels, lean slot kernels and fp32-mixed without batch_lean,
+ * user Hamiltonians, teams of workgroups, chunked shards - is served set by set through the single evaluation: the same results, no
+ * speed-up.
  * After either call the handle holds no stored trajectory (the state and observable getters and the operator-level adjoint sweep return
  * QD_ERR_STATE) and its control table is stale: the next single evaluation returns what it returned before.  qd_last_mean_applies is
  * the mean over all sets, qd_last_kernel names the sweep kernels that ran. */
@@ -430,7 +436,8 @@ int qd_set_precision(qd_handle* h, int precision);
  * contracts fast - the reference's Neumann iteration, or the diagonal-split one on 3x20-class systems and on states beyond LDS: auto = there, 0 = always the
  * Krylov kernels), gmres_poly (degree of the polynomial preconditioner, 0 = tuned then frozen, 1 = none), krylov_tau (double: the one-vector
  * path of the lean kernels' Krylov solvers accepts at residual <= krylov_tau x the reference's tolerance, default 0.1), krylov_restart (restart length of those solvers' generic path, 1 .. 14), force_neumann, var (kernel variant), no_mfma,
- * no_lean64, lean64_sb, no_collean, no_col_krylov, col_min_n, big_team, big_spread, big_blocked, traj_budget_mb (double).  Every key is also read from the
+ * no_lean64, lean64_sb, no_collean, no_col_krylov, col_min_n, big_team, big_spread, big_blocked, traj_budget_mb (double), batch_lean (the parameter-set
+ * batch shares launches on the lean slot and fp32-mixed families too: see qd_optim_evalF_batch; 0 = default).  Every key is also read from the
  * environment variable QD_<KEY> once, at qd_create (tests, measurements).  Unknown keys: QD_ERR_INVALID. */
 int qd_set_option(qd_handle* h, const char* key, const char* value);
 int qd_get_precision(const qd_handle* h);

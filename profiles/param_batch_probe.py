@@ -1,9 +1,12 @@
 """Parameter-set batch probe (run on the GPU box): what several control vectors in one sweep launch buy on the small BASELINE
-configurations, whose single sweeps leave most of the device idle (C1: 4 one-wave workgroups, C3: 16).
-For nset in 1, 2, 4, 16, 64, 256: ONE evalGradF_batch / evalF_batch call against the same sets as nset consecutive evalGradF / evalF
-calls - alternating, each twice, in one process on one lease; the comparator is the single-evaluation path as it was.  Wall-clock times
-(the host side is part of what a caller of either form pays).  The control vectors are the workload's own scaled by 1 ... 3.
-usage: param_batch_probe.py [c1 c3 ...] > profiles/param_batch_probe.txt"""
+configurations, whose single sweeps leave most of the device idle (C1: 4 one-wave workgroups, C3: 16), and - with option batch_lean = 1 -
+on the lean slot and fp32-mixed families (q4: 256 states, one dependent chain each; c5: 1024 chains on 256 CUs; c2f32: the fp32-mixed
+2x2x2 system, 64 one-wave workgroups).
+For every nset: ONE evalGradF_batch / evalF_batch call against the same sets as nset consecutive evalGradF / evalF calls - alternating,
+each twice, in one process on one lease; the comparator is the single-evaluation path as it was (for q4, c5 and c2f32 that loop is what a
+batch call runs without the option).  Wall-clock times (the host side is part of what a caller of either form pays).  The control
+vectors are the workload's own scaled by 1 ... 3.  Nothing here asserts a speed-up.
+usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 ...] > profiles/param_batch_probe.txt"""
 import os
 import sys
 import time
@@ -15,13 +18,23 @@ sys.path.insert(0, _r)
 from quandary_amd import capi  # noqa: E402
 from quandary_amd.workloads import workload_spec  # noqa: E402
 
-NSETS = (1, 2, 4, 16, 64, 256)
+# name -> (workload, precision, options, nset values)
+PROBES = {
+    "c1": ("c1", "f64", {}, (1, 2, 4, 16, 64, 256)),
+    "c3": ("c3", "f64", {}, (1, 2, 4, 16, 64, 256)),
+    "q4": ("q4", "f64", {"batch_lean": "1"}, (1, 2, 4, 8, 16)),
+    "c5": ("c5", "f64", {"batch_lean": "1"}, (1, 2, 4, 8, 16)),
+    "c2f32": ("c2", "f32mixed", {"batch_lean": "1"}, (1, 2, 4, 16, 64)),
+}
 for which in (sys.argv[1:] or ["c1", "c3"]):
+    workload, precision, options, nsets = PROBES[which]
     for grad in (True, False):
-        sp = workload_spec(which, "gradient" if grad else "simulation", {})
+        sp = workload_spec(workload, "gradient" if grad else "simulation", {})
+        sp.precision = precision
+        sp.options = {**(getattr(sp, "options", None) or {}), **options}
         h = capi.Handle(sp)
         o = capi.Optim(h, sp)
-        for nset in NSETS:
+        for nset in nsets:
             alphas = np.stack([sp.params0 * (1.0 + 2.0 * j / max(nset - 1, 1)) for j in range(nset)])
             batch = (lambda: o.evalGradF_batch(alphas)) if grad else (lambda: o.evalF_batch(alphas))
             single = (lambda: [o.evalGradF(a) for a in alphas]) if grad else (lambda: [o.evalF(a) for a in alphas])

@@ -168,6 +168,8 @@ struct TuneOpts {
   int gmres_split = -1;    // "gmres_split": linearsolver_type = gmres served by the diagonal-split iteration under GMRES's stopping rule where that
                            // iteration contracts fast (-1 = there, 0 = never: always the Krylov kernels, 1 = wherever it is built)
   int neumann_split = -1;  // "neumann_split": diagonal-split Neumann iteration (-1 = where it pays, 0 = never, 1 = wherever it is built)
+  int batch_lean = 0;      // "batch_lean": the parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch) also shares launches on the lean slot and
+                           // fp32-mixed families where their solver is a stationary iteration (0 = those go set by set, the default; 1 = one launch)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
   double sched_wait_s = 0.0;    // "sched_wait_s": seconds a time slice may wait for its predecessor (0 = automatic: 4 s x the processes that share the
                                 // device (QD_DEVICE_SHARERS, set by the launchers that put several ranks on one GPU) x the slice length in units of 1000 steps)
@@ -249,6 +251,11 @@ hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose
 // the same lean slot kernel instantiated in fp64: Neumann sweeps of the 2^5 Lindblad system (QD_PRECISION_F64)
 bool lean64_available(const DevSys& S, const TuneOpts& o);
 hipError_t launch_sweep_lean64(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+// the stationary-iteration sweeps of both lean slot families with one control table per set of a.nb_set states (qd_q32.hip compiled
+// with -DQD_SETS=1: k_forward_q32_sets / k_adjoint_q32_sets); a Krylov request is an error.  The uncoupled 2^5 system picks one or two
+// elements per thread from ALL states of the launch, a.nb = sets x states per set (option lean64_sb pins it, as for the single sweep)
+hipError_t launch_sweep_f32_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+hipError_t launch_sweep_lean64_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
 // lean column kernels (qd_col.hip): Lindblad Neumann sweeps of density matrices with 33..64 rows and runtime level counts
 bool collean_available(const DevSys& S, const TuneOpts& o);

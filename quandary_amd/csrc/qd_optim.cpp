@@ -958,14 +958,18 @@ extern "C" int qd_optim_evalGradF_dist(qd_optim* o, qd_comm* c, const double* al
 // Parameter-set batch: evalF / evalGradF at nset control vectors at once (single rank).
 // Concurrent path - the sweep's plan is the general kernel family with one workgroup per state, standard Hamiltonian
 // model, fp64, a shard whose trajectory fits without chunking: ONE launch per sweep over nset x nlocal states, set j
-// reading its own control table (SweepArgs::nb_set / ctl_set, the SETS instantiations of k_forward / k_adjoint).  The
+// reading its own control table (SweepArgs::nb_set / ctl_set, the SETS instantiations of k_forward / k_adjoint).  With
+// option batch_lean = 1 (default 0) also the lean slot family and the fp32-mixed sweeps, where the plan's kernel solver
+// is a stationary iteration - a neumann request or a gmres request served by the stand-in (k_forward_q32_sets /
+// k_adjoint_q32_sets, qd_q32.hip); a Krylov plan (gmres_split = 0) goes set by set: those kernels have no set axis.  The
 // local batch is replicated once per set; trajectory, stages, coefficients and results are indexed by the state as in
 // any batch.  Forward all sets, then every set's sums, objective and adjoint seeds from ITS OWN reduced cost
 // (Schroedinger + Jtrace, src/optimproblem.cpp:495-511) through the code of the single evaluation, adjoint all sets,
 // coefficient reduction and k_grad once per set - each set's numbers come out of the same operations in the same order
 // as qd_optim_evalGradF's.  Sets whose trajectories exceed what one evaluation may allocate (trajectory_fits) go in
-// equal groups of the largest size that fits.  Everything else - lean slot / lean column / global-memory families,
-// fp32-mixed, user Hamiltonians, teams, chunked shards - is served set by set through the single evaluation.
+// equal groups of the largest size that fits.  Everything else - lean column / global-memory families, lean slot and
+// fp32-mixed without the option, user Hamiltonians, teams, chunked shards - is served set by set through the single
+// evaluation.
 // ---------------------------------------------------------------------------------------------------------------
 static int ensure_replicas(qd_optim* o, int g) {
   if (g <= o->batch_replicas) return QD_OK;
@@ -1015,8 +1019,9 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
     // one plan for all sets: the per-set batch size, the row bound maximised over the sets
     h->sets = nset;
     const SweepPlan plan = h->plan_sweep(nl, false);
-    bool concurrent = plan.family == Family::General && plan.team == 1 && !h->S.dense && h->precision == QD_PRECISION_F64 && nset <= 65535 &&
-                      h->batch_ctl_set() <= 0xffffffffull;  // (grid.y of the per-set kernels; SweepArgs::ctl_set is 32 bits wide)
+    // (fp32-mixed is a family of its own: trajectory, stages and replicas follow the handle's precision, qd_handle::traj_doubles)
+    bool concurrent = plan.sweeps_sets(h->opts) && plan.team == 1 && !h->S.dense && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
+                      nset <= 65535 && h->batch_ctl_set() <= 0xffffffffull;  // (grid.y of the per-set kernels; SweepArgs::ctl_set is 32 bits wide)
     if (concurrent) {
       group = nset;
       if (grad_mode) {  // the stored trajectory and stages of a group: within what a single evaluation may allocate

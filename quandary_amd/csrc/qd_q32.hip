@@ -26,6 +26,26 @@
 
 #include "qd_device.h"
 
+// With -DQD_SETS=1 (an object of its own, build/qd_q32_sets.o): the SETS form of the stationary-iteration sweep kernels,
+// k_forward_q32_sets / k_adjoint_q32_sets, and their launchers - nothing else.  State b reads its step rows from the control table of
+// set b / SweepArgs::nb_set (parameter-set batch, qd_optim_evalGradF_batch with option batch_lean), the addressing sweep_ctl<true>
+// gives the general kernels; everything else a workgroup touches is indexed by the state.  The kernel name and the table a sweep reads
+// are the only two places where the forms differ: without the define this file preprocesses to the text it had before they existed.
+#ifndef QD_SETS
+#define QD_SETS 0
+#endif
+#if QD_SETS
+#define QD_Q32_FORWARD k_forward_q32_sets
+#define QD_Q32_ADJOINT k_adjoint_q32_sets
+#define QD_Q32_CTL(A) (A.ctl + (size_t)((unsigned)blockIdx.x / (unsigned)A.nb_set) * A.ctl_set)
+#else
+#define QD_Q32_FORWARD k_forward_q32
+#define QD_Q32_ADJOINT k_adjoint_q32
+#define QD_Q32_CTL(A) A.ctl
+#endif
+#define QD_Q32_STR2(x) #x
+#define QD_Q32_STR(x) QD_Q32_STR2(x)
+
 namespace qd {
 
 constexpr float F32_SOLVER_TOL = 2.384185791015625e-07f;  // 2^-22
@@ -1151,7 +1171,7 @@ template <> struct ZTraj<double> {
 // forward sweep (TimeStepper::solveODE for every initial condition of the batch)
 // ---------------------------------------------------------------------------------------------
 template <int Q, int SB, typename R, bool GM = false, bool HJ = false>
-__global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && !GM && sizeof(R) == 4 && Q == 5 ? QD_F32HJ_W : Q32<Q, SB, R>::MINW >> ((GM && sizeof(R) == 4) || HJ ? 1 : 0))) k_forward_q32(const SweepArgs A) {
+__global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && !GM && sizeof(R) == 4 && Q == 5 ? QD_F32HJ_W : Q32<Q, SB, R>::MINW >> ((GM && sizeof(R) == 4) || HJ ? 1 : 0))) QD_Q32_FORWARD(const SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef Team32<Q, SB, R, GM, HJ> TM;
   typedef typename TM::f2 f2;
@@ -1174,7 +1194,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
   vm_drain();
   for (int s = 0; s < A.nsub; s++) {
     StepC<Q> c;
-    load_step_k<Q>(A.ctl + (size_t)s * A.cs, c, HJ);
+    load_step_k<Q>(QD_Q32_CTL(A) + (size_t)s * A.cs, c, HJ);
     tm.st.prep(c);
     const R hf = uniform((R)c.h);
     f2 xs[EPT];
@@ -1246,7 +1266,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
 // adjoint sweep (TimeStepper::solveAdjointODE + ImplMidpoint::evolveBWD + compute_dRHS_dParams)
 // ---------------------------------------------------------------------------------------------
 template <int Q, int SB, typename R, bool GM = false, bool HJ = false>
-__global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && !GM && sizeof(R) == 4 && Q == 5 ? QD_F32HJ_W : Q32<Q, SB, R>::MINW >> ((GM && sizeof(R) == 4) || HJ ? 1 : 0))) k_adjoint_q32(const SweepArgs A) {
+__global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && !GM && sizeof(R) == 4 && Q == 5 ? QD_F32HJ_W : Q32<Q, SB, R>::MINW >> ((GM && sizeof(R) == 4) || HJ ? 1 : 0))) QD_Q32_ADJOINT(const SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef Team32<Q, SB, R, GM, HJ> TM;
   typedef typename TM::f2 f2;
@@ -1282,7 +1302,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
       }
     }
     StepC<Q> c;
-    load_step_k<Q>(A.ctl + (size_t)s * A.cs, c, HJ);
+    load_step_k<Q>(QD_Q32_CTL(A) + (size_t)s * A.cs, c, HJ);
     tm.st.prep(c);
     const R hf = uniform((R)c.h);
     // ImplMidpoint::evolveBWD (timestepper.cpp:631-694).  The primal stage z = x + h/2 k of the sub-step (:640-652) was stored by
@@ -1336,6 +1356,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
   }
 }
 
+#if !QD_SETS
 // single operator application (test hook: qd_apply_rhs with QD_PRECISION_F32MIXED; timing loop of the MFMA measurement)
 template <int Q, int SB, typename R, bool HJ = false>
 __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (Q32<Q, SB, R>::MINW >> (HJ ? 1 : 0))) k_apply_q32(const DevSys S, const double* __restrict__ ctlrow, int transpose,
@@ -1486,6 +1507,8 @@ __global__ void __launch_bounds__(64) k_apply_mfma32(const DevSys S, const doubl
   }
 }
 
+#endif  // !QD_SETS
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -1500,13 +1523,14 @@ static hipError_t go_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   const size_t lds = Team32<Q, SB, R, GM, HJ>::lds_bytes();
   // (the forward kernel named first: the compiler emits the kernels in the order they are first named, and its code for two of them
   //  has been seen to depend on that order - profiles/HISTORY.md, "One launcher for both directions")
-  auto kf = !adjoint ? k_forward_q32<Q, SB, R, GM, HJ> : k_adjoint_q32<Q, SB, R, GM, HJ>;
+  auto kf = !adjoint ? QD_Q32_FORWARD<Q, SB, R, GM, HJ> : QD_Q32_ADJOINT<Q, SB, R, GM, HJ>;
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
-  note_kernel(adjoint ? 1 : 0, adjoint ? "k_adjoint_q32" : "k_forward_q32", Q, SB, type_name<R>(), GM, HJ);
+  note_kernel(adjoint ? 1 : 0, adjoint ? QD_Q32_STR(QD_Q32_ADJOINT) : QD_Q32_STR(QD_Q32_FORWARD), Q, SB, type_name<R>(), GM, HJ);
   hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
   return hipGetLastError();
 }
+#if !QD_SETS
 template <int Q, int SB, typename R, bool HJ = false>
 static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const double* x, double* y, int nb, int nrep, hipStream_t st) {
   constexpr int nt = Q32<Q, SB, R>::NT;
@@ -1518,17 +1542,45 @@ static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const do
   hipLaunchKernelGGL(kf, dim3(nb), dim3(nt), lds, st, S, ctlrow, tr, x, y, nrep);
   return hipGetLastError();
 }
+#endif
 
 // Elements per thread of the uncoupled 2^5 kernels, as a power of two, in both precisions.  Small batches (at most one state per CU: the
 // shards of a multi-GPU run, BASELINE config 5 on 8 GPUs) run two elements per thread on 512 threads - two waves per SIMD hide part of
 // the latency one 256-thread group per CU leaves exposed: 128 states x 1000 steps, fp64 gradient, one lease: 16.1 -> 15.0 ms (forward
 // 5.5 -> 5.3).  Larger batches keep two 256-thread groups per CU, four elements per thread; so do the Krylov kernels (the only form built).
+// A sets launch (parameter-set batch) counts every state of the launch, a.nb = sets x states of one set, because that is what fills the
+// chip: a batch may run <5, 2, ...> where the single evaluation of the same shard runs <5, 1, ...>.  The option lean64_sb pins it for both.
 static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
   if (a.use_gmres) return 2;
   if (o.lean64_sb == 1 || o.lean64_sb == 2) return o.lean64_sb;
   return a.nb <= 256 ? 1 : 2;
 }
 
+#if QD_SETS
+// The sweeps of a parameter-set batch: a.nb states = a.nb / a.nb_set sets, each reading its own control table.  The instantiations are
+// those the launchers below pick for a stationary iteration; the Krylov kernels have no SETS form (their degree tuner keeps statistics
+// per handle that a launch of mixed sets would blur): a request for one is an error, never another kernel.
+static bool sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
+hipError_t launch_sweep_f32_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  if (!sets_args_ok(a)) return hipErrorInvalidValue;
+  if (a.S.hasJ) {
+    if (a.S.Q == 5) return go_sweep<5, 1, float, false, true>(a, adjoint, st);
+    if (a.S.Q == 4) return go_sweep<4, 0, float, false, true>(a, adjoint, st);
+    return hipErrorInvalidValue;
+  }
+  if (a.S.Q == 5) return lean64_sb(a, o) == 1 ? go_sweep<5, 1, float>(a, adjoint, st) : go_sweep<5, 2, float>(a, adjoint, st);
+  if (a.S.Q == 4) return go_sweep<4, 0, float>(a, adjoint, st);
+  if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);
+  return hipErrorInvalidValue;
+}
+hipError_t launch_sweep_lean64_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  if (!sets_args_ok(a) || (a.S.Q != 4 && a.S.Q != 5)) return hipErrorInvalidValue;
+  if (a.S.Q == 4 && a.S.hasJ) return go_sweep<4, 0, double, false, true>(a, adjoint, st);
+  if (a.S.Q == 5 && a.S.hasJ) return go_sweep<5, 1, double, false, true>(a, adjoint, st);
+  if (a.S.Q == 4) return go_sweep<4, 0, double>(a, adjoint, st);
+  return lean64_sb(a, o) == 1 ? go_sweep<5, 1, double>(a, adjoint, st) : go_sweep<5, 2, double>(a, adjoint, st);
+}
+#else
 hipError_t launch_sweep_f32(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
   if (a.S.hasJ) {  // [r6] dipole-dipole coupling: the coupled stencils in fp32 (stationary iterations only)
     if (a.use_gmres) return hipErrorInvalidValue;
@@ -1590,5 +1642,6 @@ hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transp
   if (S.Q == 4) return go_app<4, 0, double>(S, ctlrow, transpose, x, y, nb, 1, st);
   return go_app<5, 2, double>(S, ctlrow, transpose, x, y, nb, 1, st);
 }
+#endif  // QD_SETS
 
 }  // namespace qd
