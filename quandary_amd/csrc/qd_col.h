@@ -34,6 +34,15 @@ constexpr int col_max_threads(int ept) { return ept == 5 ? 768 : 64 * ((64 + ept
 
 __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// Ket class of a wave by the level i'_0 of oscillator 0 that all its columns share (USLOT): at the bottom level there is no ket-down
+// neighbour of oscillator 0, at the top level no ket-up neighbour and no T1 term.  KET_NONE: nothing known, every term is formed.
+enum : int { KET_NONE = 0, KET_BOTTOM = 1, KET_INTERIOR = 2, KET_TOP = 3 };
+// Wave order of the class-form forward kernel (ColTeam's KCLS): 0 = plain, 1 = one wave of every class per SIMD (COLFLAGS; measured
+// slower on the 3 x 20 headline, 541.7 against 535.8 ms, profiles/ketedge_ab.txt: not the default)
+#ifndef QD_COL_KET_PERMUTE
+#define QD_COL_KET_PERMUTE 0
+#endif
+
 // SPLIT: the kernels of the diagonal-split solver keep (1 - alpha D)^-1 per element instead of the diagonal itself; the diagonal is then
 // re-derived where the full operator is applied (once or twice per step) from a row part held by the thread and a column part in LDS
 // USLOT: every column of a wave has the same level indices i'_k of the oscillators k < L (post[k] a multiple of EPT, no idle columns):
@@ -95,12 +104,19 @@ struct ColLean {
   static __host__ __device__ unsigned tab_off(int N) { return 2 * bufbytes(N) + 2 * (unsigned)sizeof(double) * NRED * (unsigned)(ncols(N) / EPT) + 128; }
   static size_t lds_bytes(int N) { return (size_t)tab_off(N) + 48 * (size_t)ncols(N); }
 
+  // PERM (USLOT): wave w takes the column block EPT (w / n_0) of level w % n_0 of oscillator 0 - consecutive waves, which share a SIMD
+  // every fourth, are of different ket classes
+  template <bool PERM = false>
   __device__ __forceinline__ void init(const DevSys& S, unsigned char* sm) {
     smem = sm;
     N = S.N;
     const int lane = threadIdx.x & 63;
     const int w = uniform_i((int)(threadIdx.x >> 6));
     col0 = w * EPT;
+    if constexpr (PERM) {
+      const int n0 = S.n[0];
+      if ((int)(blockDim.x >> 6) % n0 == 0) col0 = uniform_i(S.post[0] * (w % n0) + EPT * (w / n0));
+    }
     row = lane;
     rowok = lane < N;
     // zero the exchange buffers once: padding rows and idle columns are read (with zero coefficients) and must stay finite
@@ -280,9 +296,11 @@ struct ColLean {
   // y = M x (TRANS = false) or M^T x at slot j (ColStencil::apply of qd_device.h; its S.hasJ block = HJ here)
   // NODIAG: only the off-diagonal part C = M - diag(M) (the diagonal-split solver applies the diagonal in closed form)
   // acc: added to the result (the accumulators start there: no extra instruction)
-  template <bool TRANS, bool NODIAG = false>
+  // KC: ket class of the wave (forward NODIAG form only): the terms of oscillator 0 that the class does not have are not formed
+  template <bool TRANS, bool NODIAG = false, int KC = KET_NONE>
   __device__ __forceinline__ double2 apply(const StepC<Q>& c, int j, const double2 own, const double2 prev, const double2 next,
                                            const double2* acc = nullptr) const {
+    static_assert(KC == KET_NONE || (!TRANS && NODIAG && USLOT && !HJ && Q > 1), "class forms: the forward stage pass");
     double ar = acc ? acc->x : 0.0, ai = acc ? acc->y : 0.0;
     if (!NODIAG) {
       double dwj, ddj;
@@ -291,8 +309,32 @@ struct ColLean {
       ar = fma(dwj, own.y, acc ? fma(ddj, own.x, ar) : ddj * own.x);
       ai = fma(-dwj, own.x, acc ? fma(ddj, own.y, ai) : ddj * own.y);
     }
+    if constexpr (KC != KET_NONE) {
+      // oscillator 0 of a wave of known class (never the stride-1 oscillator): the bra neighbours, the ket neighbours there are, and
+      // the T1 term with the coefficient set_alpha has formed whole
+      const double2 xu = ld(aru[0] + (unsigned)j * COLB), xd = ld(ard[0] + (unsigned)j * COLB);
+      double er = su[0] * xu.x, ei = su[0] * xu.y;     // U1 - D2
+      double fr = -sd[0] * xd.x, fi = -sd[0] * xd.y;  // U2 - D1
+      if constexpr (KC != KET_BOTTOM) {
+        const double2 xdp = ld(tb + (unsigned)ocd[0][0] + (unsigned)j * COLB);
+        er = fma(-cy[0][0], xdp.x, er);
+        ei = fma(-cy[0][0], xdp.y, ei);
+      }
+      if constexpr (KC != KET_TOP) {
+        const double2 xup = ld(tb + (unsigned)ocu[0][0] + (unsigned)j * COLB);
+        fr = fma(cx[0][0], xup.x, fr);
+        fi = fma(cx[0][0], xup.y, fi);
+      }
+      ar = fma(c.q[0], er + fr, fma(c.p[0], ei - fi, ar));
+      ai = fma(c.q[0], ei + fi, fma(-c.p[0], er - fr, ai));
+      if constexpr (KC != KET_TOP) {  // T1 off-diagonal term (the top class has none)
+        const double2 xl = ld(aru[0] + (unsigned)ocu[0][0] + (unsigned)j * COLB);
+        ar = fma(g1u[0], xl.x, ar);
+        ai = fma(g1u[0], xl.y, ai);
+      }
+    }
 #pragma unroll
-    for (int k = 0; k < Q; k++) {
+    for (int k = KC != KET_NONE ? 1 : 0; k < Q; k++) {
       double2 xu, xd, xup, xdp;
       nbrs(k, j, own, prev, next, xu, xd, xup, xdp);
       const double er = fma(-cyv(j, k), xdp.x, su[k] * xu.x), ei = fma(-cyv(j, k), xdp.y, su[k] * xu.y);  // U1 - D2
@@ -360,10 +402,14 @@ typedef double col_d2 __attribute__((ext_vector_type(2)));
 // per-workgroup machinery: buffers, reductions, the Neumann solver
 // SKIP: the solver skips stopping tests (stage / neumann below) - an instantiation of its own (a request with a relative tolerance
 // that can bind, rel2 >= 1e-30, keeps the test-every-pass kernels; with both forms in one kernel the second code path cost 11 %)
-template <int Q, int EPT, bool SPLIT = false, bool USLOT = false, bool SKIP = false, bool HJ = false>
+// KCLS: the forward kernel of the diagonal-split stationary solver on waves of one ket class each (USLOT, no coupling) - stage() runs
+// the class form of the pass (and, under QD_COL_KET_PERMUTE, the waves are permuted: ColLean::init<PERM>)
+template <int Q, int EPT, bool SPLIT = false, bool USLOT = false, bool SKIP = false, bool HJ = false, bool KCLS = false>
 struct ColTeam {
+  static_assert(!KCLS || (SPLIT && USLOT && !HJ && Q > 1), "ket classes: diagonal-split form, uniform slots, no coupling");
   typedef ColLean<Q, EPT, SPLIT, USLOT, HJ> ST;
   ST st;
+  int kc;  // KCLS: the wave's ket class
   double* red;
   float4* fred;  // two slots of 16 partial sums of the solver's fp32 norm reduction
   int redslot, nw;
@@ -373,7 +419,11 @@ struct ColTeam {
   int lastn, lastna;  // passes of the previous forward sub-step (stage) / iterations of the previous linear solve (neumann)
 
   __device__ __forceinline__ void init(const DevSys& S, unsigned char* smem) {
-    st.init(S, smem);
+    st.template init<KCLS && QD_COL_KET_PERMUTE>(S, smem);
+    if constexpr (KCLS) {
+      const int lv = st.col0 / S.post[0];
+      kc = uniform_i(S.n[0] < 2 ? KET_NONE : lv == 0 ? KET_BOTTOM : lv == S.n[0] - 1 ? KET_TOP : KET_INTERIOR);
+    }
     red = reinterpret_cast<double*>(smem + 2 * ST::bufbytes(S.N));
     redslot = 0;
     nw = (int)(blockDim.x >> 6);
@@ -398,9 +448,29 @@ struct ColTeam {
     __syncthreads();
   }
 
+  // slot of the wave's partial sums in the reduction buffers: its column block - the wave id, except under the permuted wave order of
+  // KCLS, where the sums are still added in column order
+  __device__ __forceinline__ int wslot() const { return KCLS ? uniform_i(st.col0 / EPT) : (int)(threadIdx.x >> 6); }
   template <int NV>
   __device__ __forceinline__ void sum(double (&v)[NV]) {
-    block_sum<NV, false>(v, red + redslot * NRED * nw);
+    if constexpr (KCLS) {  // block_sum with the partial sums in wslot()
+      double* r = red + redslot * NRED * nw;
+#pragma unroll
+      for (int i = 0; i < NV; i++) v[i] = wave_sum(v[i]);
+      if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; i++) r[i * nw + wslot()] = v[i];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < NV; i++) {
+        double t = 0.0;
+        for (int w = 0; w < nw; w++) t += r[i * nw + w];
+        v[i] = t;
+      }
+    } else {
+      block_sum<NV, false>(v, red + redslot * NRED * nw);
+    }
     redslot ^= 1;
   }
   // Workgroup sum of NV <= 4 values for the Krylov solver [r6]: the wave level is a reduce-scatter (row r of 16 lanes ends up with the
@@ -465,7 +535,7 @@ struct ColTeam {
     float4* rf = fred + redslot * 4;
     redslot ^= 1;
     v = wave_sum_f32(v);
-    if ((threadIdx.x & 63) == 0) reinterpret_cast<float*>(rf)[threadIdx.x >> 6] = v;
+    if ((threadIdx.x & 63) == 0) reinterpret_cast<float*>(rf)[wslot()] = v;
     __syncthreads();
     const float4 a = rf[0], b = rf[1], c = rf[2], d = rf[3];
     return (((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w))) + (((c.x + c.y) + (c.z + c.w)) + ((d.x + d.y) + (d.z + d.w)));
@@ -491,6 +561,8 @@ struct ColTeam {
       static_assert(!TRANS && SPLIT, "the forward operator of the diagonal-split solver");
 #pragma unroll
       for (int k = 0; k < Q; k++) st.g1u[k] = (alpha * S.g1off[k]) * st.su[k];
+      // (KCLS: the ket factor of oscillator 0 is one per wave - the whole T1 coefficient, the product the pass would form)
+      if constexpr (KCLS) st.g1u[0] *= st.cx[0][0];
     }
     palpha = alpha;
 #pragma unroll
@@ -591,7 +663,8 @@ struct ColTeam {
   // SPLIT: the step size is folded into the coefficients (set_alpha<false, true> has scaled the thread's part): a pass forms
   // x + alpha C z with its accumulators started at x - two fp64 instructions per element less.
   __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, const double2 (&x)[EPT], double2 (&z)[EPT]) {
-    const double sc = A.inv_abs2 / (alpha * alpha);
+    double sc = A.inv_abs2 / (alpha * alpha);
+    if constexpr (KCLS) sc = to_scalar(sc);  // (wave-uniform: a scalar operand of the tested passes instead of a register pair of every pass)
     StepC<Q> ca = c;  // (alpha p, alpha q, alpha cs, alpha sn: scaled in VALU once per sub-step, back to scalar registers)
 #pragma unroll
     for (int k = 0; k < (SPLIT ? Q : 0); k++) {
@@ -609,6 +682,23 @@ struct ColTeam {
 #pragma unroll
     for (int j = 0; j < EPT; j++) z[j] = x[j];
     const int skip = SKIP ? lastn - (A.standin_tau2 != 0.f ? 4 : 3) : 0;
+    // KCLS: one copy of the pass loop per ket class behind a wave-uniform branch; everything above is computed once, in front of it, and
+    // the copies share the exit below (a wave of an unclassified system, n_0 = 1, runs the interior copy: every term)
+    int iter;
+    if constexpr (KCLS) {
+      if (kc == KET_TOP) iter = passes<KET_TOP>(A, ca, alpha, sc, skip, rel2, thr, d0, dprev, x, z);
+      else if (kc == KET_BOTTOM) iter = passes<KET_BOTTOM>(A, ca, alpha, sc, skip, rel2, thr, d0, dprev, x, z);
+      else iter = passes<KET_INTERIOR>(A, ca, alpha, sc, skip, rel2, thr, d0, dprev, x, z);
+    } else {
+      iter = passes<KET_NONE>(A, ca, alpha, sc, skip, rel2, thr, d0, dprev, x, z);
+    }
+    if (SKIP) lastn = iter + 1;
+    return iter + 1;
+  }
+  // the pass loop of stage() in the form of ket class KC (ColLean::apply), on stage()'s own variables; returns the index of the last pass
+  template <int KC>
+  __device__ __forceinline__ int passes(const SweepArgs& A, const StepC<Q>& c, double alpha, double sc, int skip, float& rel2, float& thr, float& d0,
+                                        float& dprev, const double2 (&x)[EPT], double2 (&z)[EPT]) {
     int iter;
     for (iter = -1; iter < A.maxiter; iter++) {
       const unsigned wa = st.tb + (unsigned)st.dlt;
@@ -619,7 +709,7 @@ struct ColTeam {
         const double2 own = z[j];
         double2 w;
         if constexpr (SPLIT) {
-          w = st.template apply<false, true>(ca, j, own, prev, z[j + 1 < EPT ? j + 1 : j], &x[j]);  // x + alpha C z
+          w = st.template apply<false, true, KC>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j], &x[j]);  // x + alpha C z
         } else {
           const double2 t = st.template apply<false, false>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j]);
           w.x = fma(alpha, t.x, x[j].x);
@@ -666,8 +756,7 @@ struct ColTeam {
       dprev = d;
       if (stop) { iter++; break; }
     }
-    if (SKIP) lastn = iter + 1;
-    return iter + 1;
+    return iter;
   }
 
   // ---------------------------------------------------------------------------------------------
@@ -1103,7 +1192,8 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   static_assert(!KRY || (SPLIT && !SKIP), "the Krylov solver runs on the diagonal-split form");
   constexpr bool HJ = QD_COL_HJ;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef ColTeam<Q, EPT, SPLIT, USLOT, SKIP, HJ> TM;
+  // (ket classes: where the waves share the level of oscillator 0 - stationary diagonal-split solver, no coupling)
+  typedef ColTeam<Q, EPT, SPLIT, USLOT, SKIP, HJ, SPLIT && USLOT && !KRY && !HJ> TM;
   const DevSys& S = A.S;
   TM tm;
   tm.init(S, smem);
