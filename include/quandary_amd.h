@@ -362,11 +362,14 @@ int qd_optim_last_chunks(const qd_optim* o);
  * the row bound maximised over them.  Sets whose stored trajectories together exceed what one evaluation may allocate (option
  * traj_budget_mb) are swept in equal groups of the largest size that fits.
  * Option batch_lean (qd_set_option; 0 = default, 1 = on): the concurrent path also serves the lean slot family (2^4 / 2^5 all-qubit
- * Lindblad systems, fp64) and the fp32-mixed sweeps, wherever the kernel's linear solver is a stationary iteration - a neumann request,
- * or a gmres request served by the stand-in; their Krylov kernels (gmres_split = 0) keep going set by set.  The uncoupled 2^5 system
+ * Lindblad systems, fp64), the fp32-mixed sweeps and the lean column family (Lindblad systems of two or three oscillators with 33..64
+ * rows, with or without dipole-dipole coupling: the 3 x 20 class), wherever the kernel's linear solver is a stationary iteration - a
+ * neumann request, or a gmres request served by the stand-in; their Krylov kernels (gmres_split = 0) keep going set by set.  A lean
+ * column batch is time-sliced by the states of the whole launch (option col_slices), so it may be sliced where the single evaluation is
+ * not: the same arithmetic per step, the penalty sums added slice by slice.  The uncoupled 2^5 system
  * picks one or two elements per thread from the states of the whole launch, nset x ninit, so a batch may run another instantiation
  * than the single evaluation of the same shard (option lean64_sb pins it for both).  Off by default (profiles/param_batch_probe.txt has what it buys).
- * Fallback: every other configuration - lean column and global-memory kernels, lean slot kernels and fp32-mixed without batch_lean,
+ * Fallback: every other configuration - global-memory kernels, lean slot, fp32-mixed and lean column kernels without batch_lean,
  * user Hamiltonians, teams of workgroups, chunked shards - is served set by set through the single evaluation: the same results, no
  * speed-up.
  * After either call the handle holds no stored trajectory (the state and observable getters and the operator-level adjoint sweep return
@@ -437,7 +440,7 @@ int qd_set_precision(qd_handle* h, int precision);
  * Krylov kernels), gmres_poly (degree of the polynomial preconditioner, 0 = tuned then frozen, 1 = none), krylov_tau (double: the one-vector
  * path of the lean kernels' Krylov solvers accepts at residual <= krylov_tau x the reference's tolerance, default 0.1), krylov_restart (restart length of those solvers' generic path, 1 .. 14), force_neumann, var (kernel variant), no_mfma,
  * no_lean64, lean64_sb, no_collean, no_col_krylov, col_min_n, big_team, big_spread, big_blocked, traj_budget_mb (double), batch_lean (the parameter-set
- * batch shares launches on the lean slot and fp32-mixed families too: see qd_optim_evalF_batch; 0 = default).  Every key is also read from the
+ * batch shares launches on the lean slot, fp32-mixed and lean column families too: see qd_optim_evalF_batch; 0 = default).  Every key is also read from the
  * environment variable QD_<KEY> once, at qd_create (tests, measurements).  Unknown keys: QD_ERR_INVALID. */
 int qd_set_option(qd_handle* h, const char* key, const char* value);
 int qd_get_precision(const qd_handle* h);

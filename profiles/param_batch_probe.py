@@ -1,12 +1,15 @@
 """Parameter-set batch probe (run on the GPU box): what several control vectors in one sweep launch buy on the small BASELINE
 configurations, whose single sweeps leave most of the device idle (C1: 4 one-wave workgroups, C3: 16), and - with option batch_lean = 1 -
 on the lean slot and fp32-mixed families (q4: 256 states, one dependent chain each; c5: 1024 chains on 256 CUs; c2f32: the fp32-mixed
-2x2x2 system, 64 one-wave workgroups).
+2x2x2 system, 64 one-wave workgroups) and on the lean column family, one workgroup = one CU per state (c4pure / c4diag: the 3 x 20
+Lindblad system with the C4 constants over 250 steps from one initial condition - the reference's AxC case, ONE workgroup - and from the
+60 diagonal ones; c4jpure / c4jdiag: the same with Jkl = 1.0, the coupled kernels).
 For every nset: ONE evalGradF_batch / evalF_batch call against the same sets as nset consecutive evalGradF / evalF calls - alternating,
-each twice, in one process on one lease; the comparator is the single-evaluation path as it was (for q4, c5 and c2f32 that loop is what a
-batch call runs without the option).  Wall-clock times (the host side is part of what a caller of either form pays).  The control
+each twice, in one process on one lease; the comparator is the single-evaluation path as it was (for q4, c5, c2f32 and the c4 probes
+that loop is what a batch call runs without the option).  Both times of either form are printed: the distance between the two single
+times is the noise a ratio has to be read against (nset 1 against the single call above all).  Wall-clock times (the host side is part of what a caller of either form pays).  The control
 vectors are the workload's own scaled by 1 ... 3.  Nothing here asserts a speed-up.
-usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 ...] > profiles/param_batch_probe.txt"""
+usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag ...] > profiles/param_batch_probe.txt"""
 import os
 import sys
 import time
@@ -18,18 +21,23 @@ sys.path.insert(0, _r)
 from quandary_amd import capi  # noqa: E402
 from quandary_amd.workloads import workload_spec  # noqa: E402
 
-# name -> (workload, precision, options, nset values)
+# name -> (workload, precision, options, nset values, configuration overrides)
+COL = (1, 2, 4, 16, 64)
 PROBES = {
-    "c1": ("c1", "f64", {}, (1, 2, 4, 16, 64, 256)),
-    "c3": ("c3", "f64", {}, (1, 2, 4, 16, 64, 256)),
-    "q4": ("q4", "f64", {"batch_lean": "1"}, (1, 2, 4, 8, 16)),
-    "c5": ("c5", "f64", {"batch_lean": "1"}, (1, 2, 4, 8, 16)),
-    "c2f32": ("c2", "f32mixed", {"batch_lean": "1"}, (1, 2, 4, 16, 64)),
+    "c1": ("c1", "f64", {}, (1, 2, 4, 16, 64, 256), {}),
+    "c3": ("c3", "f64", {}, (1, 2, 4, 16, 64, 256), {}),
+    "q4": ("q4", "f64", {"batch_lean": "1"}, (1, 2, 4, 8, 16), {}),
+    "c5": ("c5", "f64", {"batch_lean": "1"}, (1, 2, 4, 8, 16), {}),
+    "c2f32": ("c2", "f32mixed", {"batch_lean": "1"}, (1, 2, 4, 16, 64), {}),
+    "c4pure": ("c4", "f64", {"batch_lean": "1"}, COL, {"ntime": 250, "initialcondition": "pure, 0, 0"}),
+    "c4diag": ("c4", "f64", {"batch_lean": "1"}, COL, {"ntime": 250, "initialcondition": "diagonal"}),
+    "c4jpure": ("c4", "f64", {"batch_lean": "1"}, COL, {"ntime": 250, "initialcondition": "pure, 0, 0", "Jkl": 1.0}),
+    "c4jdiag": ("c4", "f64", {"batch_lean": "1"}, COL, {"ntime": 250, "initialcondition": "diagonal", "Jkl": 1.0}),
 }
 for which in (sys.argv[1:] or ["c1", "c3"]):
-    workload, precision, options, nsets = PROBES[which]
+    workload, precision, options, nsets, overrides = PROBES[which]
     for grad in (True, False):
-        sp = workload_spec(workload, "gradient" if grad else "simulation", {})
+        sp = workload_spec(workload, "gradient" if grad else "simulation", overrides)
         sp.precision = precision
         sp.options = {**(getattr(sp, "options", None) or {}), **options}
         h = capi.Handle(sp)

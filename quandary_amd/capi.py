@@ -555,7 +555,9 @@ class Optim:
 
     # several control vectors in one sweep launch (parameter-set batch): alphas [nset, ndesign]
     def evalF_batch(self, alphas):
-        """qd_optim_evalF_batch: the objective at every row of alphas; a list of dicts, set j as evalF(alphas[j])."""
+        """qd_optim_evalF_batch: the objective at every row of alphas; a list of dicts, set j as evalF(alphas[j]).  The sets share one
+        launch per sweep on the general kernel family and, with option batch_lean = 1, on the stationary iterations of the lean slot,
+        fp32-mixed and lean column families; everything else is served set by set (last_batch_sets)."""
         alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1, self.h.ndesign) if self.h.ndesign else np.zeros((len(alphas), 0))
         nset = alphas.shape[0]
         vals = (qd_objective_value * max(nset, 1))()
@@ -563,7 +565,8 @@ class Optim:
         return [vals[j].as_dict() for j in range(nset)]
 
     def evalGradF_batch(self, alphas):
-        """qd_optim_evalGradF_batch: (list of dicts, gradients [nset, ndesign]), set j as evalGradF(alphas[j])."""
+        """qd_optim_evalGradF_batch: (list of dicts, gradients [nset, ndesign]), set j as evalGradF(alphas[j]).  Which sweeps share a
+        launch: see evalF_batch."""
         alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1, self.h.ndesign) if self.h.ndesign else np.zeros((len(alphas), 0))
         nset = alphas.shape[0]
         vals = (qd_objective_value * max(nset, 1))()
@@ -573,7 +576,8 @@ class Optim:
 
     @property
     def last_batch_sets(self):
-        """Sets that shared one sweep launch in the last batch call (1 = served set by set through the single evaluation)."""
+        """Sets that shared one sweep launch in the last batch call (1 = served set by set through the single evaluation: a Krylov
+        plan, the global-memory family, a lean slot / fp32-mixed / lean column sweep without option batch_lean)."""
         return self.lib.qd_optim_last_batch_sets(self._o)
 
     # multi-GPU: every rank calls with the RCCL communicator (qd_comm*) created for the same rank / nranks

@@ -17,6 +17,22 @@
 
 #include "qd_device.h"
 
+// With QD_COL_SETS 1 (set by qd_col_sets.hip / qd_colj_sets.hip before the include, objects of their own): the SETS form of the
+// stationary-iteration sweeps, k_*_col_sets / k_*_colj_sets - the same templates, compiled a second time.  The task of initial condition
+// ic reads its step rows from the control table of set ic / SweepArgs::nb_set (parameter-set batch, qd_optim_evalGradF_batch with option
+// batch_lean), the addressing sweep_ctl<true> of qd_device.h gives the general kernels: wave-uniform, so the rows stay scalar loads.
+// Trajectory, primal stages, coefficients, carry buffers and scheduler words stay indexed by ic.  The table address and the kernel names
+// are the only places where the device code of the forms differs; on the host side col_sweep refuses the Krylov solver, which has no
+// SETS form.  Without the flag this file preprocesses to the text it had before the form existed.
+#ifndef QD_COL_SETS
+#define QD_COL_SETS 0
+#endif
+#if QD_COL_SETS
+#define QD_COL_CTL(A, ic) (A.ctl + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * A.ctl_set)
+#else
+#define QD_COL_CTL(A, ic) A.ctl
+#endif
+
 namespace qd {
 
 constexpr unsigned COLB = 1024;  // bytes per padded column: 64 rows x 16 B
@@ -1237,7 +1253,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
 
   for (int s = s_lo; s < s_hi; s++) {
     StepC<Q> c;
-    load_step_k<Q>(A.ctl + (size_t)s * A.cs, c, HJ);
+    load_step_k<Q>(QD_COL_CTL(A, ic) + (size_t)s * A.cs, c, HJ);
     if (SPLIT) tm.template set_alpha<false, SPLIT && !KRY>(S, 0.5 * c.h);
     if (A.traj) store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, x, true);
     // the sub-step in stage form (ColTeam::stage): x is the right-hand side of the solve and stays in registers
@@ -1398,7 +1414,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
       }
     }
     StepC<Q> c;
-    load_step_k<Q>(A.ctl + (size_t)s * A.cs, c, HJ);
+    load_step_k<Q>(QD_COL_CTL(A, ic) + (size_t)s * A.cs, c, HJ);
     // ImplMidpoint::evolveBWD (timestepper.cpp:631-694); the primal stage z of the sub-step was stored by the forward sweep
     if (SPLIT) tm.template set_alpha<true>(S, 0.5 * c.h);
     double2 kb[EPT];  // adjoint stage: (I - h/2 M)^T kbar = xbar ; kbar *= h
@@ -1553,7 +1569,11 @@ static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  if (a.use_gmres) return go(yes, no, yes);
+  if constexpr (QD_COL_SETS) {  // (no SETS form of the Krylov kernels: an error, and nothing instantiated)
+    if (a.use_gmres) return hipErrorInvalidValue;
+  } else {
+    if (a.use_gmres) return go(yes, no, yes);
+  }
   if constexpr (QD_COL_HJ) {
     return a.neumann_split ? go(yes, no, no) : hipErrorInvalidValue;
   } else {
@@ -1592,5 +1612,26 @@ static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const
     if ((S).Q == 3) return (S).N <= 60 ? FN<3, 5>(__VA_ARGS__) : FN<3, 8>(__VA_ARGS__); \
     return hipErrorInvalidValue;                                                       \
   } while (0)
+
+#if QD_COL_SETS
+// The SETS units: a.nb states = a.nb / a.nb_set sets, each reading its own control table.  A request they cannot serve - the Krylov
+// solver, states that do not divide into sets - is an error, never another kernel.
+static bool col_sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
+// One object per <Q, EPT> (QD_COL_SETS_Q, QD_COL_SETS_EPT on the command line: they compile side by side) holds that case's col_sweep and
+// with it its kernels; the object built without the two holds the unit's entry point, which reaches them through QD_COL_DISPATCH.
+template <int Q, int EPT>
+hipError_t QD_COLK(sweep_part)(const SweepArgs& a, bool adjoint, hipStream_t st);
+#ifdef QD_COL_SETS_Q
+template <>
+hipError_t QD_COLK(sweep_part)<QD_COL_SETS_Q, QD_COL_SETS_EPT>(const SweepArgs& a, bool adjoint, hipStream_t st) {
+  return col_sweep<QD_COL_SETS_Q, QD_COL_SETS_EPT>(a, adjoint, st);
+}
+#else
+template <> hipError_t QD_COLK(sweep_part)<2, 5>(const SweepArgs& a, bool adjoint, hipStream_t st);
+template <> hipError_t QD_COLK(sweep_part)<2, 8>(const SweepArgs& a, bool adjoint, hipStream_t st);
+template <> hipError_t QD_COLK(sweep_part)<3, 5>(const SweepArgs& a, bool adjoint, hipStream_t st);
+template <> hipError_t QD_COLK(sweep_part)<3, 8>(const SweepArgs& a, bool adjoint, hipStream_t st);
+#endif
+#endif
 
 }  // namespace qd

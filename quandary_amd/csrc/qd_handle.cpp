@@ -1017,7 +1017,7 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
   if (sets && (!p.sweeps_sets(opts) || p.team != 1 || S.dense || nb % sets != 0))
-    return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state - and, with option batch_lean, the stationary iterations of the lean slot and fp32-mixed families - sweeps several sets at once");
+    return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
   return QD_OK;
@@ -1063,7 +1063,7 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
     // (nb_set: the instantiations with one control table per set - a missing one is an error, never another kernel)
     case Family::F32: return a.nb_set ? launch_sweep_f32_sets(a, adjoint, opts, st) : launch_sweep_f32(a, adjoint, opts, st);
     case Family::Slot: return a.nb_set ? launch_sweep_lean64_sets(a, adjoint, opts, st) : launch_sweep_lean64(a, adjoint, opts, st);
-    case Family::Col: return launch_sweep_col(a, adjoint, st);
+    case Family::Col: return a.nb_set ? launch_sweep_col_sets(a, adjoint, st) : launch_sweep_col(a, adjoint, st);
     default:  // General and Global: the variant says which; nb_set: the instantiations with one control table per set
       if (a.nb_set) return adjoint ? launch_adjoint_sets(a, plan.cfg, st) : launch_forward_sets(a, plan.cfg, st);
       return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);

@@ -99,10 +99,10 @@ struct SweepPlan {
   bool need_big;       // ensure_big before the launch
   // the global-memory kernels store the stages in the element order of the general ones
   Family stage_layout() const { return family == Family::Global ? Family::General : family; }
-  // Kernels with a set axis exist for this plan (parameter-set batch): the general family, and under option batch_lean the lean slot
-  // and fp32-mixed families where the kernel's solver is a stationary iteration (their Krylov kernels have no SETS form)
+  // Kernels with a set axis exist for this plan (parameter-set batch): the general family, and under option batch_lean the lean slot,
+  // fp32-mixed and lean column families where the kernel's solver is a stationary iteration (their Krylov kernels have no SETS form)
   bool sweeps_sets(const TuneOpts& o) const {
-    return family == Family::General || (o.batch_lean && (family == Family::Slot || family == Family::F32) && cfg.gmres == 0);
+    return family == Family::General || (o.batch_lean && (family == Family::Slot || family == Family::F32 || family == Family::Col) && cfg.gmres == 0);
   }
 };
 

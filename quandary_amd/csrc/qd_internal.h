@@ -168,8 +168,8 @@ struct TuneOpts {
   int gmres_split = -1;    // "gmres_split": linearsolver_type = gmres served by the diagonal-split iteration under GMRES's stopping rule where that
                            // iteration contracts fast (-1 = there, 0 = never: always the Krylov kernels, 1 = wherever it is built)
   int neumann_split = -1;  // "neumann_split": diagonal-split Neumann iteration (-1 = where it pays, 0 = never, 1 = wherever it is built)
-  int batch_lean = 0;      // "batch_lean": the parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch) also shares launches on the lean slot and
-                           // fp32-mixed families where their solver is a stationary iteration (0 = those go set by set, the default; 1 = one launch)
+  int batch_lean = 0;      // "batch_lean": the parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch) also shares launches on the lean slot,
+                           // fp32-mixed and lean column families where their solver is a stationary iteration (0 = those go set by set, the default; 1 = one launch)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
   double sched_wait_s = 0.0;    // "sched_wait_s": seconds a time slice may wait for its predecessor (0 = automatic: 4 s x the processes that share the
                                 // device (QD_DEVICE_SHARERS, set by the launchers that put several ranks on one GPU) x the slice length in units of 1000 steps)
@@ -263,6 +263,11 @@ int col_slices(int nb, int ntime, const TuneOpts& o);  // time slices of a lean 
 size_t col_krylov_doubles(int nb, int nslice);  // size of SweepArgs::kry for the Krylov solver of the lean column kernels
 hipError_t launch_sweep_col(const SweepArgs& a, bool adjoint, hipStream_t st);
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st);
+// their stationary-iteration sweeps with one control table per set of a.nb_set states (qd_col_sets.hip / qd_colj_sets.hip: k_*_col_sets,
+// k_*_colj_sets, the instantiation launch_sweep_col picks for the same arguments); a Krylov request is an error.  The first forwards to
+// the second where S.hasJ.
+hipError_t launch_sweep_col_sets(const SweepArgs& a, bool adjoint, hipStream_t st);
+hipError_t launch_sweep_colj_sets(const SweepArgs& a, bool adjoint, hipStream_t st);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false);
 size_t krylov_doubles(const DevSys& S, int nb);
 size_t big_work_doubles(const DevSys& S, int nb);

@@ -959,17 +959,19 @@ extern "C" int qd_optim_evalGradF_dist(qd_optim* o, qd_comm* c, const double* al
 // Concurrent path - the sweep's plan is the general kernel family with one workgroup per state, standard Hamiltonian
 // model, fp64, a shard whose trajectory fits without chunking: ONE launch per sweep over nset x nlocal states, set j
 // reading its own control table (SweepArgs::nb_set / ctl_set, the SETS instantiations of k_forward / k_adjoint).  With
-// option batch_lean = 1 (default 0) also the lean slot family and the fp32-mixed sweeps, where the plan's kernel solver
-// is a stationary iteration - a neumann request or a gmres request served by the stand-in (k_forward_q32_sets /
-// k_adjoint_q32_sets, qd_q32.hip); a Krylov plan (gmres_split = 0) goes set by set: those kernels have no set axis.  The
+// option batch_lean = 1 (default 0) also the lean slot family, the fp32-mixed sweeps and the lean column family, where
+// the plan's kernel solver is a stationary iteration - a neumann request or a gmres request served by the stand-in
+// (k_*_q32_sets, qd_q32.hip; k_*_col_sets / k_*_colj_sets, qd_col.h); a Krylov plan (gmres_split = 0) goes set by set:
+// those kernels have no set axis.  A lean column batch is time-sliced by all its states (arm_slices sees nset x nlocal:
+// scheduler words, carry buffers and the waiting limit are sized from that), its primal stages keep the interleaved
+// layout of that family (ztraj_fmt) whatever the number of sets.  The
 // local batch is replicated once per set; trajectory, stages, coefficients and results are indexed by the state as in
 // any batch.  Forward all sets, then every set's sums, objective and adjoint seeds from ITS OWN reduced cost
 // (Schroedinger + Jtrace, src/optimproblem.cpp:495-511) through the code of the single evaluation, adjoint all sets,
 // coefficient reduction and k_grad once per set - each set's numbers come out of the same operations in the same order
 // as qd_optim_evalGradF's.  Sets whose trajectories exceed what one evaluation may allocate (trajectory_fits) go in
-// equal groups of the largest size that fits.  Everything else - lean column / global-memory families, lean slot and
-// fp32-mixed without the option, user Hamiltonians, teams, chunked shards - is served set by set through the single
-// evaluation.
+// equal groups of the largest size that fits.  Everything else - the global-memory family, the lean families without
+// the option, user Hamiltonians, teams, chunked shards - is served set by set through the single evaluation.
 // ---------------------------------------------------------------------------------------------------------------
 static int ensure_replicas(qd_optim* o, int g) {
   if (g <= o->batch_replicas) return QD_OK;
