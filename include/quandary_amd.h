@@ -357,10 +357,13 @@ int qd_optim_last_chunks(const qd_optim* o);
  * objective created with nranks > 1); nset < 1 or a null pointer: QD_ERR_INVALID; whatever a single evaluation rejects is rejected
  * the same way (gradient of pi-pulses or of the spline_amplitude parameterisation: QD_ERR_UNSUPPORTED).
  * Concurrent path: where a sweep runs on the general kernel family with one workgroup per state (the small Schroedinger and Lindblad
- * systems that leave most of the device idle), the standard Hamiltonian model, fp64 and a shard that needs no chunking, all sets
+ * systems that leave most of the device idle), fp64 and a shard that needs no chunking, all sets
  * share ONE launch per sweep - nset x ninit states, each set reading a control table of its own; one plan is made for all sets, from
- * the row bound maximised over them.  Sets whose stored trajectories together exceed what one evaluation may allocate (option
- * traj_budget_mb) are swept in equal groups of the largest size that fits.
+ * the row bound maximised over them.  User Hamiltonians (qd_set_hamiltonian) on the LDS kernels - N <= 32 Lindblad, dim <= 1024
+ * Schroedinger - are served the same way by default: every set of a launch also reads a table of G(t) = -i H(t) of its own.
+ * Sets whose stored trajectories - and, for a user Hamiltonian, G(t) tables - together exceed what one evaluation may allocate (option
+ * traj_budget_mb) are swept in equal groups of the largest size that fits; the G(t) tables of one group stay within the 16 GB
+ * qd_set_hamiltonian allows one table, in forward-only calls too.
  * Option batch_lean (qd_set_option; 0 = default, 1 = on): the concurrent path also serves the lean slot family (2^4 / 2^5 all-qubit
  * Lindblad systems, fp64), the fp32-mixed sweeps and the lean column family (Lindblad systems of two or three oscillators with 33..64
  * rows, with or without dipole-dipole coupling: the 3 x 20 class), wherever the kernel's linear solver is a stationary iteration - a
@@ -369,9 +372,9 @@ int qd_optim_last_chunks(const qd_optim* o);
  * not: the same arithmetic per step, the penalty sums added slice by slice.  The uncoupled 2^5 system
  * picks one or two elements per thread from the states of the whole launch, nset x ninit, so a batch may run another instantiation
  * than the single evaluation of the same shard (option lean64_sb pins it for both).  Off by default (profiles/param_batch_probe.txt has what it buys).
- * Fallback: every other configuration - global-memory kernels, lean slot, fp32-mixed and lean column kernels without batch_lean,
- * user Hamiltonians, teams of workgroups, chunked shards - is served set by set through the single evaluation: the same results, no
- * speed-up.
+ * Fallback: every other configuration - global-memory kernels (user Hamiltonians beyond dim 1024 among them), lean slot, fp32-mixed
+ * and lean column kernels without batch_lean, teams of workgroups, chunked shards - is served set by set through the single
+ * evaluation: the same results, no speed-up.
  * After either call the handle holds no stored trajectory (the state and observable getters and the operator-level adjoint sweep return
  * QD_ERR_STATE) and its control table is stale: the next single evaluation returns what it returned before.  qd_last_mean_applies is
  * the mean over all sets, qd_last_kernel names the sweep kernels that ran. */

@@ -556,7 +556,7 @@ class Optim:
     # several control vectors in one sweep launch (parameter-set batch): alphas [nset, ndesign]
     def evalF_batch(self, alphas):
         """qd_optim_evalF_batch: the objective at every row of alphas; a list of dicts, set j as evalF(alphas[j]).  The sets share one
-        launch per sweep on the general kernel family and, with option batch_lean = 1, on the stationary iterations of the lean slot,
+        launch per sweep on the general kernel family (user Hamiltonians up to dim 1024 included) and, with option batch_lean = 1, on the stationary iterations of the lean slot,
         fp32-mixed and lean column families; everything else is served set by set (last_batch_sets)."""
         alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1, self.h.ndesign) if self.h.ndesign else np.zeros((len(alphas), 0))
         nset = alphas.shape[0]

@@ -2629,6 +2629,14 @@ __device__ __forceinline__ const double* sweep_ctl(const SweepArgs& A, int ic0) 
   if constexpr (SETS) return A.ctl + (size_t)(ic0 / A.nb_set) * A.ctl_set;
   else return A.ctl;
 }
+// The table of G(t) = -i H(t) of a workgroup's state (dense user Hamiltonians): S.gtab itself, named inside the expression that forms
+// c.g as before.  SETS: the set's own table, A.gtab_set doubles behind the previous set's (k_gmat with the sets on grid.y) - a
+// wave-uniform address like the control table's.
+template <bool SETS>
+__device__ __forceinline__ const double* sweep_gtab(const SweepArgs& A, const DevSys& S, int ic0) {
+  if constexpr (SETS) return S.gtab + (size_t)(ic0 / A.nb_set) * A.gtab_set;
+  else return S.gtab;
+}
 
 // SETS: parameter-set batch - the states are sets of A.nb_set, each set with a control table of its own, A.ctl_set doubles apart
 // (qd_optim_evalGradF_batch); everything else is indexed by the state as in any batch.  false: one table, the kernels as they were.
@@ -2684,7 +2692,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward(const SweepArgs 
       load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)s * A.cs, c, jpairs);
       scalarize<Q>(c, jpairs);
     }
-    c.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)s * S.N * S.N : nullptr;
+    c.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)s * S.N * S.N : nullptr;
     tm.st.prep(S, tm.L, c);
     if (traj) {
 #pragma unroll
@@ -2862,7 +2870,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
       StepC<Q> c1;
       load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, c1, jpairs);  // M(tstop of step s) = row s + 1
       if (TM::V::LEAN) scalarize<Q>(c1, jpairs);
-      c1.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)(s + 1) * S.N * S.N : nullptr;
+      c1.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)(s + 1) * S.N * S.N : nullptr;
       tm.st.prep(S, tm.L, c1);
       const double hneg = -sweep_ctl<SETS>(A, tm.ic0)[(size_t)s * A.cs];
       tm.publish(xp);
@@ -3007,7 +3015,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
       load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)s * A.cs, c, jpairs);
     }
     if (TM::V::LEAN) scalarize<Q>(c, jpairs);
-    c.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)s * S.N * S.N : nullptr;
+    c.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)s * S.N * S.N : nullptr;
     tm.st.prep(S, tm.L, c);
     double cf[2 * Q];
 #pragma unroll
@@ -3035,7 +3043,7 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs 
       store_coeffs();
       StepC<Q> c1;
       load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, c1, jpairs);
-      c1.g = S.dense ? reinterpret_cast<const double2*>(S.gtab) + (size_t)(s + 1) * S.N * S.N : nullptr;
+      c1.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)(s + 1) * S.N * S.N : nullptr;
       tm.st.prep(S, tm.L, c1);
       tm.publish(xb);
       collect_coeffs();

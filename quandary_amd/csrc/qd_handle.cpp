@@ -71,7 +71,7 @@ extern "C" void qd_destroy(qd_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
-  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad}) b->release();
+  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab}) b->release();
   h->h_bparams.release();
   h->h_betable.release();
   h->h_bgrad.release();
@@ -525,11 +525,28 @@ int qd_handle::batch_begin(const double* alphas, int nset) {
   for (double hh : sched_h) batch_bound.amax = std::max(batch_bound.amax, fabs(hh) / 2.0);
   params_set = true;  // (the gates have controls to look at)
   traj_valid = false;
+  bgtab_sets = 0;  // (the G(t) tables of an earlier call belong to other controls)
+  return QD_OK;
+}
+
+// Dense user Hamiltonians: G(t) of every table row of the sets [first, first + nsets) of the call, from the control tables batch_begin
+// has written - k_gmat with the sets on grid.y, the arithmetic of refresh_tables element by element.  Per group of sets, so that the
+// tables in memory are those of the launches that read them.
+int qd_handle::batch_gtables(int first, int nsets) {
+  if (!S.dense) return QD_OK;
+  QD_HIP(qd::use_device(device));
+  int r;
+  if ((r = d_bgtab.ensure((size_t)nsets * batch_gtab_set()))) return r;
+  QD_HIP(launch_gmat_sets(S, d_g0.p, d_btable.p + (size_t)first * batch_ctl_set(), batch_ctl_set(), cs, (int)sched_t.size(), d_bgtab.p,
+                          batch_gtab_set(), nsets, stream));
+  bgtab_first = first;
+  bgtab_sets = nsets;
   return QD_OK;
 }
 
 void qd_handle::batch_end() {
   sets = 0;
+  bgtab_sets = 0;
   batch_first = 0;
   traj_valid = false;
   params_dirty = true;  // (the next ordinary sweep evaluates its own table again)
@@ -977,6 +994,12 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   a.ctl = h->sets ? h->batch_table() : h->d_table.p;
   a.nb_set = h->sets ? nb / h->sets : 0;
   a.ctl_set = h->sets ? (unsigned)h->batch_ctl_set() : 0u;
+  if (h->sets && h->S.dense) {  // the group's G(t) tables, the first set's in the place of the handle's own
+    if (h->bgtab_first != h->batch_first || h->bgtab_sets < h->sets || h->batch_gtab_set() > 0xffffffffull)
+      return fail(QD_ERR_STATE, "parameter-set batch on a user Hamiltonian: the G(t) tables of the sets being swept have not been built (qd_handle::batch_gtables), or one table exceeds the 32-bit set stride");
+    a.S.gtab = h->d_bgtab.p;
+    a.gtab_set = (unsigned)h->batch_gtab_set();
+  }
   a.cs = h->cs;
   a.nsub = h->nsub;
   a.nstages = h->nstages;
@@ -1016,8 +1039,8 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
-  if (sets && (!p.sweeps_sets(opts) || p.team != 1 || S.dense || nb % sets != 0))
-    return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
+  if (sets && (!p.sweeps_sets(opts) || p.team != 1 || nb % sets != 0))
+    return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state (standard model or user Hamiltonian) - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
   return QD_OK;

@@ -99,8 +99,9 @@ struct SweepPlan {
   bool need_big;       // ensure_big before the launch
   // the global-memory kernels store the stages in the element order of the general ones
   Family stage_layout() const { return family == Family::Global ? Family::General : family; }
-  // Kernels with a set axis exist for this plan (parameter-set batch): the general family, and under option batch_lean the lean slot,
-  // fp32-mixed and lean column families where the kernel's solver is a stationary iteration (their Krylov kernels have no SETS form)
+  // Kernels with a set axis exist for this plan (parameter-set batch): the general family - the standard model and the dense user
+  // Hamiltonians of the LDS kernels alike -, and under option batch_lean the lean slot, fp32-mixed and lean column families where the
+  // kernel's solver is a stationary iteration (their Krylov kernels have no SETS form)
   bool sweeps_sets(const TuneOpts& o) const {
     return family == Family::General || (o.batch_lean && (family == Family::Slot || family == Family::F32 || family == Family::Col) && cfg.gmres == 0);
   }
@@ -236,6 +237,12 @@ struct qd_handle {
   int batch_first = 0;             // first set of the group being swept (tables of all sets of the call are resident)
   qd::RowBound batch_bound{};
   qd::DBuf d_bparams, d_btable, d_betable, d_bgrad;
+  // dense user Hamiltonians: the group's tables of G(t) = -i H(t), one per set, batch_gtab_set() doubles apart (batch_gtables; the
+  // handle's own d_gtab and S.gtab are left alone like d_table)
+  qd::DBuf d_bgtab;
+  int bgtab_first = 0, bgtab_sets = 0;  // the sets whose tables d_bgtab holds (0 sets = none)
+  size_t batch_gtab_set() const { return S.dense ? sched_t.size() * (size_t)S.N * S.N * 2 : 0; }  // the rows of batch_ctl_set() x N^2 complex
+  int batch_gtables(int first, int nsets);  // G(t) tables of the sets [first, first + nsets) from their control tables, one launch
   qd::HBuf h_bparams, h_betable, h_bgrad;
   size_t batch_ctl_set() const { return sched_t.size() * (size_t)cs; }    // rows the step table really has x cs
   size_t batch_etable_set() const { return etimes.size() * (size_t)cs; }

@@ -3,8 +3,9 @@
 // kernels for the kernel variants that make sense for that case and exports plain launch functions
 // for the dispatcher in qd_kernels.hip.
 // With -DQD_SETS=1 (objects of their own, build/qd_sets_*.o): the SETS form of the same sweep kernels - one control table per set of
-// SweepArgs::nb_set states (parameter-set batch, qd_optim_evalGradF_batch) - for the variants with one workgroup per state in LDS and
-// the standard Hamiltonian model; no operator application, no global-memory kernels.
+// SweepArgs::nb_set states (parameter-set batch, qd_optim_evalGradF_batch) - for the variants with one workgroup per state in LDS, of
+// the standard Hamiltonian model (QD_B = 0 | 1) and of the dense user Hamiltonians (QD_B = 2: variants 11, 12, 13, 15, 17, one G(t) table
+// per set as well, SweepArgs::gtab_set); no operator application, no global-memory kernels (variant 16).
 #include "qd_device.h"
 #include "qd_big.h"
 
@@ -16,9 +17,6 @@
 constexpr bool kGmPart = (QD_PART >= 2);
 #ifndef QD_SETS
 #define QD_SETS 0
-#endif
-#if QD_SETS && QD_B == 2
-#error "the SETS kernels are built for the standard Hamiltonian model only (QD_B = 0 | 1)"
 #endif
 constexpr bool kSets = (QD_SETS != 0);
 

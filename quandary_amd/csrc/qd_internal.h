@@ -133,6 +133,9 @@ struct SweepArgs {
   unsigned ctl_set;  // parameter-set batch: doubles between two sets' tables = (rows of one table) x cs
   unsigned* sched;
   int col_noskip;  // lean column kernels: test the stopping rule in every pass (option col_skip = 0)
+  // parameter-set batch of a dense user Hamiltonian: doubles between two sets' G(t) tables = (rows of one table) x N^2 x 2, S.gtab being
+  // the first set's (sweep_gtab<SETS>, qd_device.h; in what was padding behind col_noskip, like nb_set and ctl_set)
+  unsigned gtab_set;
   unsigned long long sched_ticks;  // wall_clock64 ticks (100 MHz) a slice may wait for its predecessor before the error word is raised
   double* stash;        // [2][nb][2*dim] staging area of the several-elements-per-thread variants (adjoint state / midpoint state
                         // parked in L2/HBM while a linear solve runs, instead of compiler-chosen scratch spills)
@@ -220,7 +223,8 @@ hipError_t launch_apply(const DevSys& S, const double* ctlrow, int transpose, co
                         const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-// the same sweeps with one control table per set of a.nb_set states (qd_inst_sets.hip): standard Hamiltonian model, every LDS variant
+// the same sweeps with one control table per set of a.nb_set states (qd_inst.hip with -DQD_SETS=1): every LDS variant, of the standard
+// Hamiltonian model and of the dense user Hamiltonians (one G(t) table per set, a.gtab_set)
 hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 // control tables of nset parameter vectors in one launch: params [nset][ndesign] -> table [nset][nrows][cs], table2 [nset][nrows2][cs]
@@ -228,6 +232,9 @@ hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int n
                                 double* table, const double* times2, const double* hs2, int nrows2, double* table2, int cs,
                                 unsigned long long* zero_me, hipStream_t st);
 hipError_t launch_gmat(const DevSys& S, const double* g0, const double* table, int cs, int nrows, double* gtab, hipStream_t st);
+// G(t) tables of nset parameter sets in one launch: set j reads table + j * ctl_set and writes gtab + j * gtab_set (strides in doubles)
+hipError_t launch_gmat_sets(const DevSys& S, const double* g0, const double* table, size_t ctl_set, int cs, int nrows, double* gtab,
+                            size_t gtab_set, int nset, hipStream_t st);
 hipError_t launch_objective(const DevSys& S, const DevTarget& tg, const double* x, int nb, double* out4, hipStream_t st);
 hipError_t launch_seed(const DevSys& S, const DevTarget& tg, const double* x, const double* rbar_ibar, int nb, double* xbar,
                        hipStream_t st);

@@ -419,12 +419,15 @@ __global__ void k_seed_weights(const double* __restrict__ sums, const double* __
 // dense user-Hamiltonian path: G(t_row) = -i Hsys + sum_k q_k Im(Hc_k) - i p_k Re(Hc_k) for every row of
 // the control table (Re = Ad + sum q_k Ac_k, Im = Bd + sum p_k Bc_k with Ac = Im(Hc), Bc = -Re(Hc):
 // src/mastereq.cpp:760-795, src/hamiltonianfilereader.cpp:77-84,170-176)
+// grid.y = parameter sets (launch_gmat_sets): set j reads the control table table + j * ctl_set and writes gtab + j * gtab_set.
 // ---------------------------------------------------------------------------------------------
 __global__ void k_gmat(const DevSys S, const double* __restrict__ g0, const double* __restrict__ table, int cs, int nrows,
-                       double* __restrict__ gtab) {
+                       double* __restrict__ gtab, size_t ctl_set, size_t gtab_set) {
   const int nn = S.N * S.N;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (size_t)nrows * nn) return;
+  table += (size_t)blockIdx.y * ctl_set;
+  gtab += (size_t)blockIdx.y * gtab_set;
   const int row = (int)(e / nn), el = (int)(e % nn);
   const double* r = table + (size_t)row * cs;
   double re = g0[2 * el], im = g0[2 * el + 1];
@@ -687,7 +690,7 @@ static const apply_fn app_tab[3][2][8] = {{QD_ROW8(inst_apply_, 0, 0), QD_ROW8(i
                                           {QD_ROW8(inst_apply_, 0, 1), QD_ROW(inst_apply_, 1, 1)},
                                           {QD_ROW8(inst_apply_, 0, 2), QD_ROW8(inst_apply_, 1, 2)}};
 
-// the SETS form of the same kernels (qd_inst.hip with -DQD_SETS=1): standard Hamiltonian model only, index [qubit][lindblad][Q-1]
+// the SETS form of the same kernels (qd_inst.hip with -DQD_SETS=1), index [qubit][lindblad][Q-1] like the tables above
 #define QD_DECLS(q, l, b)                                                                        \
   hipError_t inst_forwardsets_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t); \
   hipError_t inst_adjointsets_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
@@ -695,21 +698,26 @@ static const apply_fn app_tab[3][2][8] = {{QD_ROW8(inst_apply_, 0, 0), QD_ROW8(i
 QD_DECLS_Q(0, 0) QD_DECLS_Q(1, 0) QD_DECLS_Q(0, 1) QD_DECLS_Q(1, 1)
 QD_DECLS(6, 0, 0) QD_DECLS(7, 0, 0) QD_DECLS(8, 0, 0) QD_DECLS(6, 0, 1) QD_DECLS(7, 0, 1) QD_DECLS(8, 0, 1)
 QD_DECLS(6, 1, 0) QD_DECLS(7, 1, 0) QD_DECLS(8, 1, 0)
-static const sweep_fn fwd_sets_tab[2][2][8] = {{QD_ROW8(inst_forwardsets_, 0, 0), QD_ROW8(inst_forwardsets_, 1, 0)},
-                                               {QD_ROW8(inst_forwardsets_, 0, 1), QD_ROW(inst_forwardsets_, 1, 1)}};
-static const sweep_fn adj_sets_tab[2][2][8] = {{QD_ROW8(inst_adjointsets_, 0, 0), QD_ROW8(inst_adjointsets_, 1, 0)},
-                                               {QD_ROW8(inst_adjointsets_, 0, 1), QD_ROW(inst_adjointsets_, 1, 1)}};
+QD_DECLS_Q(0, 2) QD_DECLS_Q(1, 2)
+QD_DECLS(6, 0, 2) QD_DECLS(7, 0, 2) QD_DECLS(8, 0, 2) QD_DECLS(6, 1, 2) QD_DECLS(7, 1, 2) QD_DECLS(8, 1, 2)
+static const sweep_fn fwd_sets_tab[3][2][8] = {{QD_ROW8(inst_forwardsets_, 0, 0), QD_ROW8(inst_forwardsets_, 1, 0)},
+                                               {QD_ROW8(inst_forwardsets_, 0, 1), QD_ROW(inst_forwardsets_, 1, 1)},
+                                               {QD_ROW8(inst_forwardsets_, 0, 2), QD_ROW8(inst_forwardsets_, 1, 2)}};
+static const sweep_fn adj_sets_tab[3][2][8] = {{QD_ROW8(inst_adjointsets_, 0, 0), QD_ROW8(inst_adjointsets_, 1, 0)},
+                                               {QD_ROW8(inst_adjointsets_, 0, 1), QD_ROW(inst_adjointsets_, 1, 1)},
+                                               {QD_ROW8(inst_adjointsets_, 0, 2), QD_ROW8(inst_adjointsets_, 1, 2)}};
 
-// a.nb states = a.nb / a.nb_set sets; a missing instantiation (dense operator, global-memory kernels) is an error, never another kernel
+// a.nb states = a.nb / a.nb_set sets; a missing instantiation (the global-memory kernels, variant 16) is an error, never another kernel;
+// so is a dense operator without the stride of its G(t) tables
 hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 1 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
-      !fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
+  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 2 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
+      (cfg.qubit == 2) != (a.S.dense != 0) || (a.S.dense && (!a.S.gtab || !a.gtab_set)) || !fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
     return hipErrorInvalidValue;
   return fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
 }
 hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 1 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
-      !adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
+  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 2 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
+      (cfg.qubit == 2) != (a.S.dense != 0) || (a.S.dense && (!a.S.gtab || !a.gtab_set)) || !adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
     return hipErrorInvalidValue;
   return adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
 }
@@ -756,7 +764,16 @@ hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int n
 hipError_t launch_gmat(const DevSys& S, const double* g0, const double* table, int cs, int nrows, double* gtab, hipStream_t st) {
   const size_t total = (size_t)nrows * S.N * S.N;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, g0, table, cs, nrows, gtab);
+  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, (size_t)0, (size_t)0);
+  return hipGetLastError();
+}
+
+hipError_t launch_gmat_sets(const DevSys& S, const double* g0, const double* table, size_t ctl_set, int cs, int nrows, double* gtab,
+                            size_t gtab_set, int nset, hipStream_t st) {
+  const size_t total = (size_t)nrows * S.N * S.N;
+  if (nset < 1 || nset > 65535 || gtab_set < total * 2 || ctl_set < (size_t)nrows * cs) return hipErrorInvalidValue;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256), nset), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, ctl_set, gtab_set);
   return hipGetLastError();
 }
 

@@ -517,18 +517,21 @@ static double control_variation(const qd_handle* h, const double* alpha, double*
   return var;
 }
 
-static bool trajectory_fits(qd_handle* h, int nb, const DevTarget* tg) {
+// gsets: the nb states are this many sets of a parameter-set batch on a dense user Hamiltonian - every set's table of G(t) lies in
+// memory beside the trajectory (qd_handle::batch_gtables) and is weighed with it (0: an ordinary evaluation, or the standard model)
+static bool trajectory_fits(qd_handle* h, int nb, const DevTarget* tg, int gsets = 0) {
   size_t need;
   h->traj_doubles(nb, &need);
   if (!h->stores_full(nb, tg)) need = 0;      // (a gradient evaluation whose adjoint sweep reads the stages only)
   const size_t needz = h->ztraj_doubles(nb);  // the stored primal stages travel with the trajectory
-  need += needz;
+  const size_t needg = (size_t)gsets * h->batch_gtab_set();
+  need += needz + needg;
   if (h->opts.traj_budget_mb > 0.0)  // test hook (option traj_budget_mb): pretend HBM is this small
     return (double)need * sizeof(double) <= h->opts.traj_budget_mb * 1048576.0;
-  if (need - needz <= h->d_traj.cap && needz <= h->d_ztraj.cap) return true;
+  if (need - needz - needg <= h->d_traj.cap && needz <= h->d_ztraj.cap && needg <= h->d_bgtab.cap) return true;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-  const size_t avail = free_b + (h->d_traj.cap + h->d_ztraj.cap) * sizeof(double);
+  const size_t avail = free_b + (h->d_traj.cap + h->d_ztraj.cap + (gsets ? h->d_bgtab.cap : 0)) * sizeof(double);
   return (double)need * sizeof(double) < 0.85 * (double)avail;
 }
 
@@ -956,9 +959,11 @@ extern "C" int qd_optim_evalGradF_dist(qd_optim* o, qd_comm* c, const double* al
 
 // ---------------------------------------------------------------------------------------------------------------
 // Parameter-set batch: evalF / evalGradF at nset control vectors at once (single rank).
-// Concurrent path - the sweep's plan is the general kernel family with one workgroup per state, standard Hamiltonian
-// model, fp64, a shard whose trajectory fits without chunking: ONE launch per sweep over nset x nlocal states, set j
-// reading its own control table (SweepArgs::nb_set / ctl_set, the SETS instantiations of k_forward / k_adjoint).  With
+// Concurrent path - the sweep's plan is the general kernel family with one workgroup per state, fp64, a shard whose
+// trajectory fits without chunking: ONE launch per sweep over nset x nlocal states, set j reading its own control table
+// (SweepArgs::nb_set / ctl_set, the SETS instantiations of k_forward / k_adjoint).  A user Hamiltonian on the LDS kernels
+// (qd_set_hamiltonian, dim <= 1024) is the same family: set j also reads its own table of G(t) = -i H(t), built for the
+// sets of a launch by k_gmat with the sets on grid.y (qd_handle::batch_gtables, SweepArgs::gtab_set).  With
 // option batch_lean = 1 (default 0) also the lean slot family, the fp32-mixed sweeps and the lean column family, where
 // the plan's kernel solver is a stationary iteration - a neumann request or a gmres request served by the stand-in
 // (k_*_q32_sets, qd_q32.hip; k_*_col_sets / k_*_colj_sets, qd_col.h); a Krylov plan (gmres_split = 0) goes set by set:
@@ -970,8 +975,10 @@ extern "C" int qd_optim_evalGradF_dist(qd_optim* o, qd_comm* c, const double* al
 // (Schroedinger + Jtrace, src/optimproblem.cpp:495-511) through the code of the single evaluation, adjoint all sets,
 // coefficient reduction and k_grad once per set - each set's numbers come out of the same operations in the same order
 // as qd_optim_evalGradF's.  Sets whose trajectories exceed what one evaluation may allocate (trajectory_fits) go in
-// equal groups of the largest size that fits.  Everything else - the global-memory family, the lean families without
-// the option, user Hamiltonians, teams, chunked shards - is served set by set through the single evaluation.
+// equal groups of the largest size that fits; the G(t) tables of a group count as memory beside its trajectory and stay
+// within 16 GB together, forward-only calls included.  Everything else - the global-memory family (user Hamiltonians
+// beyond dim 1024 among them), the lean families without the option, teams, chunked shards - is served set by set
+// through the single evaluation.
 // ---------------------------------------------------------------------------------------------------------------
 static int ensure_replicas(qd_optim* o, int g) {
   if (g <= o->batch_replicas) return QD_OK;
@@ -1022,21 +1029,26 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
     h->sets = nset;
     const SweepPlan plan = h->plan_sweep(nl, false);
     // (fp32-mixed is a family of its own: trajectory, stages and replicas follow the handle's precision, qd_handle::traj_doubles)
-    bool concurrent = plan.sweeps_sets(h->opts) && plan.team == 1 && !h->S.dense && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
-                      nset <= 65535 && h->batch_ctl_set() <= 0xffffffffull;  // (grid.y of the per-set kernels; SweepArgs::ctl_set is 32 bits wide)
+    // (grid.y of the per-set kernels; SweepArgs::ctl_set and gtab_set are 32 bits wide)
+    bool concurrent = plan.sweeps_sets(h->opts) && plan.team == 1 && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
+                      nset <= 65535 && h->batch_ctl_set() <= 0xffffffffull && h->batch_gtab_set() <= 0xffffffffull;
     if (concurrent) {
-      group = nset;
-      if (grad_mode) {  // the stored trajectory and stages of a group: within what a single evaluation may allocate
+      // a user Hamiltonian: the G(t) tables of the sets of one launch together stay within what qd_set_hamiltonian allows one table
+      const double gbytes = (double)h->batch_gtab_set() * sizeof(double);
+      int lo = gbytes > 0.0 ? (int)std::min((double)nset, std::floor(16e9 / gbytes)) : nset;  // lo sets fit, hi do not
+      if (grad_mode && lo > 0) {  // the stored trajectory and stages of a group (and its G(t) tables): within what a single evaluation may allocate
         h->sets = 1;
-        int lo = trajectory_fits(h, nl, &o->tg) ? 1 : 0, hi = nset + 1;  // lo sets fit, hi do not
+        const bool dense = h->S.dense != 0;
+        int hi = lo + 1;
+        lo = trajectory_fits(h, nl, &o->tg, dense ? 1 : 0) ? 1 : 0;
         while (lo > 0 && hi - lo > 1) {
           const int mid = lo + (hi - lo) / 2;
-          if (trajectory_fits(h, mid * nl, &o->tg)) lo = mid;
+          if (trajectory_fits(h, mid * nl, &o->tg, dense ? mid : 0)) lo = mid;
           else hi = mid;
         }
-        const int ngroups = lo > 0 ? (nset + lo - 1) / lo : 0;
-        group = lo > 0 ? (nset + ngroups - 1) / ngroups : 0;  // equal groups of the largest size that fits
       }
+      const int ngroups = lo > 0 ? (nset + lo - 1) / lo : 0;
+      group = lo > 0 ? (nset + ngroups - 1) / ngroups : 0;  // equal groups of the largest size that fits
       concurrent = group > 0;  // (a shard that needs chunking for one set already: set by set)
     }
     if (concurrent) {
@@ -1047,7 +1059,7 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
         const int g = std::min(group, nset - j0), nb = g * nl;
         h->sets = g;
         h->batch_first = j0;
-        if ((r = ensure_replicas(o, g))) return r;
+        if ((r = ensure_replicas(o, g)) || (r = h->batch_gtables(j0, g))) return r;
         tgb.tstates = o->tg.tstates ? o->d_btgt.p : nullptr;
         tgb.purity = o->d_bpur.p;
         if ((r = h->forward_dev(o->d_bx0.p, nb, grad_mode, &tgb, nullptr))) return r;
