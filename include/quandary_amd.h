@@ -384,6 +384,29 @@ int qd_optim_evalGradF_batch(qd_optim* o, const double* alphas, int nset, qd_obj
  * served set by set. */
 int qd_optim_last_batch_sets(const qd_optim* o);
 
+/* Risk-neutral (robust) objective: ONE control vector on an ensemble of nvar systems that differ in Hsys - sampled transition
+ * frequencies or couplings of a device whose parameters are not known exactly - and the weighted mean of their objectives and
+ * gradients.  hsys_re / hsys_im [nvar][N*N] row-major, rad/ns.  Variant j is the handle's system with Hsys replaced by hsys[j]; the
+ * control Hamiltonians, dissipators, target, penalties and initial conditions are the handle's and the objective's.  vals [nvar] (may
+ * be NULL) and grads [nvar][ndesign] (may be NULL: then only ndesign doubles leave the device) are what qd_optim_evalGradF(alpha)
+ * returns on a handle whose qd_set_hamiltonian received hsys[j].  weights [nvar] are the caller's quadrature weights, used as given
+ * (not normalised); NULL = 1/nvar each.  Every field of *mean is sum_j w_j vals[j].field; grad_mean [ndesign] = sum_j w_j grads[j],
+ * one fma per variant in variant order (k_ensemble_mean; the regularisation terms are added to every variant's gradient before the
+ * weighting).
+ * The handle must be a user-Hamiltonian handle (qd_set_hamiltonian supplies the Hc_k): otherwise QD_ERR_STATE.  nvar < 1, a null alpha,
+ * hsys_re, hsys_im, mean or grad_mean, a negative or non-finite weight: QD_ERR_INVALID.  An objective created with nranks > 1:
+ * QD_ERR_STATE.  Whatever a single evaluation rejects is rejected the same way.
+ * The variants are the sets of a parameter-set batch (qd_optim_evalF_batch) whose control vectors are all alpha: on the LDS kernels
+ * (dim <= 1024) they share one launch per sweep, each reading a table of G(t) built from its own Hsys; groups, the one plan for all
+ * sets (the row bound of the variant with the largest row sum) and the fallback - variant by variant through the single evaluation,
+ * the same results - are those of the batch, and qd_optim_last_batch_sets reports the variants per launch.  After the call the state
+ * is that of a batch call; the handle's own Hsys is untouched and the next single evaluation returns what it returned before. */
+int qd_optim_evalF_ensemble(qd_optim* o, const double* alpha, int nvar, const double* hsys_re, const double* hsys_im,
+                            const double* weights, qd_objective_value* vals, qd_objective_value* mean);
+int qd_optim_evalGradF_ensemble(qd_optim* o, const double* alpha, int nvar, const double* hsys_re, const double* hsys_im,
+                                const double* weights, qd_objective_value* vals, qd_objective_value* mean, double* grads,
+                                double* grad_mean);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, initial conditions sharded over the ranks.
  * Replaces the reference's comm_init communicator (src/main.cpp:133-177) and its

@@ -13,7 +13,11 @@ each twice, in one process on one lease; the comparator is the single-evaluation
 that loop is what a batch call runs without the option).  Both times of either form are printed: the distance between the two single
 times is the noise a ratio has to be read against (nset 1 against the single call above all).  Wall-clock times (the host side is part of what a caller of either form pays).  The control
 vectors are the workload's own scaled by 1 ... 3.  Nothing here asserts a speed-up.
-usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 ...] > profiles/param_batch_probe.txt"""
+e22 / e16 / e27: the ensemble call (one control vector on nvar system Hamiltonians, evalGradF_ensemble / evalF_ensemble) on the systems of
+d22 / d16 / d27 against what it replaces - a loop of single evaluations over nvar handles, each prepared with its own Hsys before the
+clock starts; the variants are the workload's Hsys plus j x 0.1 % of a random Hermitian matrix of its size (64 samples span 6 %; a first run with 2 % per
+variant is recorded too: a launch lasts as long as its stiffest variant).
+usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 ...] > profiles/param_batch_probe.txt"""
 import os
 import sys
 import time
@@ -44,7 +48,54 @@ PROBES = {
     "d27": ("c2", "f64", {}, COL, {**DENSE, "nlevels": "3, 3, 3", "initialcondition": "diagonal, 1", "optim_target": "pure, 0, 0, 0",
                                    "optim_objective": "Jmeasure"}),
 }
+ENSEMBLE = {"e22": "d22", "e16": "d16", "e27": "d27"}
+
+
+def ensemble_probe(which):
+    workload, precision, options, nvars, overrides = PROBES[ENSEMBLE[which]]
+    for grad in (True, False):
+        sp = workload_spec(workload, "gradient" if grad else "simulation", overrides)
+        h = capi.Handle(sp)
+        o = capi.Optim(h, sp)
+        hsys, hc = sp.hamiltonian
+        rng = np.random.default_rng(4321)
+        a = rng.standard_normal(hsys.shape) + 1j * rng.standard_normal(hsys.shape)
+        pert = 0.001 * np.abs(hsys).max() * (a + a.conj().T)
+        own, pairs = sp.hamiltonian, []
+        for j in range(max(nvars)):  # the comparator's handles: variant j uploaded once, outside the timed region
+            sp.hamiltonian = (hsys + j * pert, hc)
+            hj = capi.Handle(sp)
+            pairs.append((hj, capi.Optim(hj, sp)))
+        sp.hamiltonian = own
+        alpha = sp.params0
+        for nvar in nvars:
+            variants = [hsys + j * pert for j in range(nvar)]
+            ens = (lambda: o.evalGradF_ensemble(alpha, variants, per_variant=False)) if grad else (lambda: o.evalF_ensemble(alpha, variants))
+            single = (lambda: [oj.evalGradF(alpha) for _, oj in pairs[:nvar]]) if grad else (lambda: [oj.evalF(alpha) for _, oj in pairs[:nvar]])
+            ens(), single()  # (allocations, solver latch, tuner)
+            t = {"ensemble": [], "single": []}
+            for rep in range(2):
+                for tag, fn in (("ensemble", ens), ("single", single)):
+                    t0 = time.perf_counter()
+                    fn()
+                    t[tag].append((time.perf_counter() - t0) * 1e3)
+                    if tag == "ensemble":
+                        sets, kern = o.last_batch_sets, h.last_kernel("forward")
+            b, s = min(t["ensemble"]), min(t["single"])
+            print(which, "grad" if grad else "fwd", "ninit", sp.ninit, "ntime", sp.time.ntime, "nvar", nvar, "variants_per_launch", sets,
+                  "ensemble_ms", " ".join("%.2f" % v for v in t["ensemble"]), "single_ms", " ".join("%.2f" % v for v in t["single"]),
+                  "single_over_ensemble %.2f" % (s / b), "ensemble_ms_per_variant %.3f" % (b / nvar), kern, flush=True)
+        for hj, oj in pairs:
+            oj.close()
+            hj.close()
+        o.close()
+        h.close()
+
+
 for which in (sys.argv[1:] or ["c1", "c3"]):
+    if which in ENSEMBLE:
+        ensemble_probe(which)
+        continue
     workload, precision, options, nsets, overrides = PROBES[which]
     for grad in (True, False):
         sp = workload_spec(workload, "gradient" if grad else "simulation", overrides)

@@ -180,6 +180,7 @@ EXPORTS = [
     "qd_comm_unique_id", "qd_comm_create", "qd_comm_create_from_file", "qd_comm_create_host", "qd_comm_backend", "qd_comm_destroy", "qd_comm_size", "qd_comm_rank",
     "qd_comm_allreduce", "qd_comm_barrier", "qd_optim_evalF_dist", "qd_optim_evalGradF_dist", "qd_optim_last_chunks", "qd_set_precision", "qd_get_precision", "qd_bench_apply_f32", "qd_get_observables", "qd_set_option",
     "qd_optim_evalF_batch", "qd_optim_evalGradF_batch", "qd_optim_last_batch_sets",
+    "qd_optim_evalF_ensemble", "qd_optim_evalGradF_ensemble",
 ]
 COMM_ID_BYTES = 128
 PRECISION = {"f64": 0, "f32mixed": 1}
@@ -250,6 +251,9 @@ def load_library(path=None):
     lib.qd_optim_evalF_batch.argtypes = [vp, c_dp, C.c_int, C.POINTER(qd_objective_value)]
     lib.qd_optim_evalGradF_batch.argtypes = [vp, c_dp, C.c_int, C.POINTER(qd_objective_value), c_dp]
     lib.qd_optim_last_batch_sets.argtypes = [vp]
+    lib.qd_optim_evalF_ensemble.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value), C.POINTER(qd_objective_value)]
+    lib.qd_optim_evalGradF_ensemble.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value),
+                                                C.POINTER(qd_objective_value), c_dp, c_dp]
     lib.qd_comm_unique_id.argtypes = [c_u8p]
     lib.qd_comm_create.argtypes = [c_u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.qd_comm_create_from_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp)]
@@ -579,6 +583,43 @@ class Optim:
         """Sets that shared one sweep launch in the last batch call (1 = served set by set through the single evaluation: a Krylov
         plan, the global-memory family, a lean slot / fp32-mixed / lean column sweep without option batch_lean)."""
         return self.lib.qd_optim_last_batch_sets(self._o)
+
+    # one control vector on several system Hamiltonians (risk-neutral objective): hsys_list [nvar] complex [N, N], rad/ns
+    def _ensemble_args(self, alpha, hsys_list, weights):
+        n = self.h.dim_rho
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        nvar = len(hsys_list)
+        hs = np.asarray(hsys_list, dtype=complex).reshape(nvar, n, n) if nvar else np.zeros((0, n, n), dtype=complex)
+        sr, si = np.ascontiguousarray(hs.real), np.ascontiguousarray(hs.imag)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(nvar)
+        return alpha, nvar, sr, si, w
+
+    def evalF_ensemble(self, alpha, hsys_list, weights=None):
+        """qd_optim_evalF_ensemble: (mean dict, list of dicts).  Variant j is this handle's system with Hsys replaced by hsys_list[j]
+        (a handle with set_hamiltonian), evaluated as evalF(alpha) on a handle that received hsys_list[j]; every field of the mean is
+        sum_j weights[j] x that field (weights as given, None = 1 / nvar each).  The variants share sweep launches like the sets of
+        evalF_batch (last_batch_sets)."""
+        alpha, nvar, sr, si, w = self._ensemble_args(alpha, hsys_list, weights)
+        vals = (qd_objective_value * max(nvar, 1))()
+        mean = qd_objective_value()
+        _check(self.lib, self.lib.qd_optim_evalF_ensemble(self._o, dptr(alpha), nvar, dptr(sr), dptr(si), dptr(w), vals, C.byref(mean)),
+               "qd_optim_evalF_ensemble")
+        return mean.as_dict(), [vals[j].as_dict() for j in range(nvar)]
+
+    def evalGradF_ensemble(self, alpha, hsys_list, weights=None, per_variant=True):
+        """qd_optim_evalGradF_ensemble: (mean dict, grad_mean [ndesign], list of dicts, gradients [nvar, ndesign] or None).
+        grad_mean = sum_j weights[j] x gradient of variant j, formed on the device; per_variant = False leaves the single gradients
+        there (grads = None)."""
+        alpha, nvar, sr, si, w = self._ensemble_args(alpha, hsys_list, weights)
+        vals = (qd_objective_value * max(nvar, 1))()
+        mean = qd_objective_value()
+        nd = self.h.ndesign
+        g = np.zeros((max(nvar, 1), max(nd, 1))) if per_variant else None
+        gm = np.zeros(max(nd, 1))
+        _check(self.lib, self.lib.qd_optim_evalGradF_ensemble(self._o, dptr(alpha), nvar, dptr(sr), dptr(si), dptr(w), vals, C.byref(mean),
+                                                              dptr(g), dptr(gm)), "qd_optim_evalGradF_ensemble")
+        return (mean.as_dict(), gm[:nd], [vals[j].as_dict() for j in range(nvar)],
+                np.ascontiguousarray(g[:nvar, :nd]) if per_variant else None)
 
     # multi-GPU: every rank calls with the RCCL communicator (qd_comm*) created for the same rank / nranks
     def evalF_dist(self, comm, alpha):

@@ -71,7 +71,7 @@ extern "C" void qd_destroy(qd_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
-  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab}) b->release();
+  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0}) b->release();
   h->h_bparams.release();
   h->h_betable.release();
   h->h_bgrad.release();
@@ -340,6 +340,23 @@ extern "C" int qd_dim_rho(const qd_handle* h) { return h ? h->S.N : QD_ERR_INVAL
 extern "C" int qd_dim_ess(const qd_handle* h) { return h ? h->dim_ess : QD_ERR_INVALID; }
 extern "C" int qd_ndesign(const qd_handle* h) { return h ? h->ndesign : QD_ERR_INVALID; }
 
+// largest row sum (and column sum, should a caller hand over a non-Hermitian matrix) of |a + i b|, N x N row-major: the Gershgorin bound
+// of the solver gates (row_bounds).  H is Hermitian, so the row sums bound the column sums too.
+static double rowsum_max(int N, const double* a, const double* b) {
+  double m = 0.0;
+  for (int i = 0; i < N; i++) {
+    double s = 0.0;
+    for (int j = 0; j < N; j++) s += hypot(a[(size_t)i * N + j], b[(size_t)i * N + j]);
+    m = std::max(m, s);
+  }
+  for (int j = 0; j < N; j++) {
+    double s = 0.0;
+    for (int i = 0; i < N; i++) s += hypot(a[(size_t)i * N + j], b[(size_t)i * N + j]);
+    m = std::max(m, s);
+  }
+  return m;
+}
+
 extern "C" int qd_set_hamiltonian(qd_handle* h, const double* hsys_re, const double* hsys_im, const double* hc_re, const double* hc_im) {
   if (!h || !hsys_re || !hsys_im) return fail(QD_ERR_INVALID, "qd_set_hamiltonian: null system Hamiltonian");
   if ((hc_re == nullptr) != (hc_im == nullptr)) return fail(QD_ERR_INVALID, "qd_set_hamiltonian: give both parts of the control Hamiltonians or neither");
@@ -358,29 +375,15 @@ extern "C" int qd_set_hamiltonian(qd_handle* h, const double* hsys_re, const dou
     std::copy(hc_re, hc_re + cr.size(), cr.begin());
     std::copy(hc_im, hc_im + ci.size(), ci.begin());
   }
-  // row sums for the Gershgorin bounds of the solver gates (row_bounds): H is Hermitian, so the row sums bound the column sums too
+  // row sums for the Gershgorin bounds of the solver gates (row_bounds)
   {
     const int N = h->S.N;
-    auto rowsum_max = [&](const double* a, const double* b) {
-      double m = 0.0;
-      for (int i = 0; i < N; i++) {
-        double s = 0.0;
-        for (int j = 0; j < N; j++) s += hypot(a[(size_t)i * N + j], b[(size_t)i * N + j]);
-        m = std::max(m, s);
-      }
-      for (int j = 0; j < N; j++) {  // (and the column sums, should a caller hand over a non-Hermitian matrix)
-        double s = 0.0;
-        for (int i = 0; i < N; i++) s += hypot(a[(size_t)i * N + j], b[(size_t)i * N + j]);
-        m = std::max(m, s);
-      }
-      return m;
-    };
     std::vector<double> zero(nn, 0.0);
-    h->dense_hsys_norm = rowsum_max(hsys_re, hsys_im);
+    h->dense_hsys_norm = rowsum_max(N, hsys_re, hsys_im);
     h->dense_hc_norm.assign(h->S.Q, 0.0);
     if (hc_re)
       for (int k = 0; k < h->S.Q; k++)
-        h->dense_hc_norm[k] = rowsum_max(hc_re + (size_t)k * nn, zero.data()) + rowsum_max(hc_im + (size_t)k * nn, zero.data());
+        h->dense_hc_norm[k] = rowsum_max(N, hc_re + (size_t)k * nn, zero.data()) + rowsum_max(N, hc_im + (size_t)k * nn, zero.data());
   }
   int r;
   if ((r = h->d_g0.ensure(g0.size())) || (r = h->d_hcr.ensure(cr.size())) || (r = h->d_hci.ensure(ci.size()))) return r;
@@ -462,7 +465,7 @@ int qd_handle::refresh_tables() {
     int r;
     if ((r = d_gtab.ensure(sched_t.size() * nn * 2))) return r;
     S.gtab = d_gtab.p;
-    QD_HIP(launch_gmat(S, d_g0.p, d_table.p, cs, (int)sched_t.size(), d_gtab.p, stream));
+    QD_HIP(launch_gmat(S, ens_g0 ? ens_g0 : d_g0.p, d_table.p, cs, (int)sched_t.size(), d_gtab.p, stream));
   }
   // asynchronous: complete at the stream synchronisation that ends the sweep (forward_dev)
   QD_HIP(hipMemcpyAsync(h_etable.p, d_etable.p, sizeof(double) * etimes.size() * cs, hipMemcpyDeviceToHost, stream));
@@ -537,10 +540,35 @@ int qd_handle::batch_gtables(int first, int nsets) {
   QD_HIP(qd::use_device(device));
   int r;
   if ((r = d_bgtab.ensure((size_t)nsets * batch_gtab_set()))) return r;
-  QD_HIP(launch_gmat_sets(S, d_g0.p, d_btable.p + (size_t)first * batch_ctl_set(), batch_ctl_set(), cs, (int)sched_t.size(), d_bgtab.p,
-                          batch_gtab_set(), nsets, stream));
+  // (an ensemble of system variants: set j of the call reads its own G0, ensemble_upload)
+  const double* g0 = ens_g0 ? ens_g0 + (size_t)first * ens_g0_set() : d_g0.p;
+  QD_HIP(launch_gmat_sets(S, g0, ens_g0 ? ens_g0_set() : 0, d_btable.p + (size_t)first * batch_ctl_set(), batch_ctl_set(), cs,
+                          (int)sched_t.size(), d_bgtab.p, batch_gtab_set(), nsets, stream));
   bgtab_first = first;
   bgtab_sets = nsets;
+  return QD_OK;
+}
+
+// Ensemble of system variants (qd_optim_evalF_ensemble): G0 = -i Hsys of the nvar variants, ens_g0_set() doubles apart in d_eg0, and
+// each variant's Gershgorin row sum as qd_set_hamiltonian forms it.  The handle's own d_g0 and dense_hsys_norm are not touched; the
+// caller points ens_g0 at what the sweeps are to read.
+int qd_handle::ensemble_upload(int nvar, const double* hsys_re, const double* hsys_im, std::vector<double>& norms) {
+  QD_HIP(qd::use_device(device));
+  const size_t nn = (size_t)S.N * S.N;
+  std::vector<double> g0((size_t)nvar * 2 * nn);
+  norms.assign(nvar, 0.0);
+  for (int j = 0; j < nvar; j++) {
+    const double *re = hsys_re + (size_t)j * nn, *im = hsys_im + (size_t)j * nn;
+    double* g = g0.data() + (size_t)j * 2 * nn;
+    for (size_t e = 0; e < nn; e++) {  // G0 = Im(Hsys) - i Re(Hsys), as in qd_set_hamiltonian
+      g[2 * e] = im[e];
+      g[2 * e + 1] = -re[e];
+    }
+    norms[j] = rowsum_max(S.N, re, im);
+  }
+  int r;
+  if ((r = d_eg0.ensure(g0.size()))) return r;
+  QD_HIP(hipMemcpy(d_eg0.p, g0.data(), sizeof(double) * g0.size(), hipMemcpyHostToDevice));
   return QD_OK;
 }
 
@@ -552,15 +580,17 @@ void qd_handle::batch_end() {
   params_dirty = true;  // (the next ordinary sweep evaluates its own table again)
 }
 
+// (grads null: the gradients stay in d_bgrad, for a reduction on the device - the ensemble mean)
 int qd_handle::batch_gradient(double ebar, int nsets, double* grads) {
   QD_HIP(qd::use_device(device));
   if (ndesign == 0) return QD_OK;
   int r;
   const size_t n = (size_t)nsets * ndesign;
-  if ((r = d_bgrad.ensure(n)) || (r = h_bgrad.ensure(n))) return r;
+  if ((r = d_bgrad.ensure(n)) || (grads && (r = h_bgrad.ensure(n)))) return r;
   const int nsub_flag = sol.stepper == QD_STEPPER_EE ? -nsub : nsub;
   QD_HIP(launch_grad_sets(dctl, d_bparams.p + (size_t)batch_first * ndesign, batch_table(), batch_ctl_set(), cs, nsub_flag, d_coeffsum.p,
                           d_betable.p + (size_t)batch_first * batch_etable_set(), batch_etable_set(), tg.ntime, ebar, d_bgrad.p, ndesign, nsets, stream));
+  if (!grads) return QD_OK;
   QD_HIP(hipMemcpyAsync(h_bgrad.p, d_bgrad.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
   QD_HIP(hipStreamSynchronize(stream));
   std::memcpy(grads, h_bgrad.p, sizeof(double) * n);

@@ -244,6 +244,14 @@ struct qd_handle {
   size_t batch_gtab_set() const { return S.dense ? sched_t.size() * (size_t)S.N * S.N * 2 : 0; }  // the rows of batch_ctl_set() x N^2 complex
   int batch_gtables(int first, int nsets);  // G(t) tables of the sets [first, first + nsets) from their control tables, one launch
   qd::HBuf h_bparams, h_betable, h_bgrad;
+  // ensemble of system variants (qd_optim_evalF_ensemble / qd_optim_evalGradF_ensemble): one control vector, nvar matrices Hsys.  d_eg0
+  // holds their G0 = -i Hsys, ens_g0_set() doubles apart.  While ens_g0 is set the G(t) tables are built from it instead of d_g0: set j of
+  // a batch from ens_g0 + j * ens_g0_set() (batch_gtables: the variants of one launch), an ordinary sweep from ens_g0 itself
+  // (refresh_tables: the variant-by-variant fallback).  dense_hsys_norm is the caller's to set beside it and to restore.
+  qd::DBuf d_eg0;
+  const double* ens_g0 = nullptr;
+  size_t ens_g0_set() const { return (size_t)2 * S.N * S.N; }
+  int ensemble_upload(int nvar, const double* hsys_re, const double* hsys_im, std::vector<double>& norms);  // norms: rowsum_max per variant
   size_t batch_ctl_set() const { return sched_t.size() * (size_t)cs; }    // rows the step table really has x cs
   size_t batch_etable_set() const { return etimes.size() * (size_t)cs; }
   const double* batch_table() const { return d_btable.p + (size_t)batch_first * batch_ctl_set(); }

@@ -232,9 +232,14 @@ hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int n
                                 double* table, const double* times2, const double* hs2, int nrows2, double* table2, int cs,
                                 unsigned long long* zero_me, hipStream_t st);
 hipError_t launch_gmat(const DevSys& S, const double* g0, const double* table, int cs, int nrows, double* gtab, hipStream_t st);
-// G(t) tables of nset parameter sets in one launch: set j reads table + j * ctl_set and writes gtab + j * gtab_set (strides in doubles)
-hipError_t launch_gmat_sets(const DevSys& S, const double* g0, const double* table, size_t ctl_set, int cs, int nrows, double* gtab,
-                            size_t gtab_set, int nset, hipStream_t st);
+// G(t) tables of nset parameter sets in one launch: set j reads table + j * ctl_set and writes gtab + j * gtab_set (strides in doubles);
+// g0_set: set j reads its own G0 = -i Hsys at g0 + j * g0_set (system variants of an ensemble), 0 = one G0 for all sets
+hipError_t launch_gmat_sets(const DevSys& S, const double* g0, size_t g0_set, const double* table, size_t ctl_set, int cs, int nrows,
+                            double* gtab, size_t gtab_set, int nset, hipStream_t st);
+// mean[i] (+)= sum_j w[j] (g[j][i] + reg[0][i] + ... + reg[nreg-1][i]) over nvar gradients [nvar][ndesign]: the addends one after the
+// other, then one fma per variant in variant order (accumulate = 0 overwrites mean)
+hipError_t launch_ensemble_mean(const double* g, const double* reg, int nreg, const double* w, int nvar, int ndesign, int accumulate,
+                                double* mean, hipStream_t st);
 hipError_t launch_objective(const DevSys& S, const DevTarget& tg, const double* x, int nb, double* out4, hipStream_t st);
 hipError_t launch_seed(const DevSys& S, const DevTarget& tg, const double* x, const double* rbar_ibar, int nb, double* xbar,
                        hipStream_t st);

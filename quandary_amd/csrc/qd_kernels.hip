@@ -420,14 +420,16 @@ __global__ void k_seed_weights(const double* __restrict__ sums, const double* __
 // the control table (Re = Ad + sum q_k Ac_k, Im = Bd + sum p_k Bc_k with Ac = Im(Hc), Bc = -Re(Hc):
 // src/mastereq.cpp:760-795, src/hamiltonianfilereader.cpp:77-84,170-176)
 // grid.y = parameter sets (launch_gmat_sets): set j reads the control table table + j * ctl_set and writes gtab + j * gtab_set.
+// g0_set: doubles between the G0 = -i Hsys of two sets (system variants of an ensemble, qd_optim_evalF_ensemble); 0 = all sets share g0.
 // ---------------------------------------------------------------------------------------------
 __global__ void k_gmat(const DevSys S, const double* __restrict__ g0, const double* __restrict__ table, int cs, int nrows,
-                       double* __restrict__ gtab, size_t ctl_set, size_t gtab_set) {
+                       double* __restrict__ gtab, size_t ctl_set, size_t gtab_set, size_t g0_set) {
   const int nn = S.N * S.N;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (size_t)nrows * nn) return;
   table += (size_t)blockIdx.y * ctl_set;
   gtab += (size_t)blockIdx.y * gtab_set;
+  g0 += (size_t)blockIdx.y * g0_set;
   const int row = (int)(e / nn), el = (int)(e % nn);
   const double* r = table + (size_t)row * cs;
   double re = g0[2 * el], im = g0[2 * el + 1];
@@ -437,6 +439,27 @@ __global__ void k_gmat(const DevSys S, const double* __restrict__ g0, const doub
   }
   gtab[2 * e] = re;
   gtab[2 * e + 1] = im;
+}
+
+// ---------------------------------------------------------------------------------------------
+// ensemble mean of the gradient (qd_optim_evalGradF_ensemble): mean[i] (+)= sum_j w[j] g[j][i] over the nvar variants of one group,
+// one fma per variant in variant order; accumulate = 0 for the first group of a call (mean is overwritten), 1 for the others.
+// reg[nreg][ndesign]: the regularisation addends of the shared control vector, added to every variant's gradient one after the other
+// before the weighting - the additions the host makes for the per-variant output, in its order, so that mean = sum_j w[j] grads[j] of
+// the gradients the caller sees.  One thread per design index.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(128) k_ensemble_mean(const double* __restrict__ g, const double* __restrict__ reg, int nreg,
+                                                       const double* __restrict__ w, int nvar, int ndesign, int accumulate,
+                                                       double* __restrict__ mean) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ndesign) return;
+  double acc = accumulate ? mean[i] : 0.0;
+  for (int j = 0; j < nvar; j++) {
+    double gj = g[(size_t)j * ndesign + i];
+    for (int k = 0; k < nreg; k++) gj += reg[(size_t)k * ndesign + i];
+    acc = fma(w[j], gj, acc);
+  }
+  mean[i] = acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -764,16 +787,26 @@ hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int n
 hipError_t launch_gmat(const DevSys& S, const double* g0, const double* table, int cs, int nrows, double* gtab, hipStream_t st) {
   const size_t total = (size_t)nrows * S.N * S.N;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, (size_t)0, (size_t)0);
+  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, (size_t)0, (size_t)0, (size_t)0);
   return hipGetLastError();
 }
 
-hipError_t launch_gmat_sets(const DevSys& S, const double* g0, const double* table, size_t ctl_set, int cs, int nrows, double* gtab,
-                            size_t gtab_set, int nset, hipStream_t st) {
+hipError_t launch_gmat_sets(const DevSys& S, const double* g0, size_t g0_set, const double* table, size_t ctl_set, int cs, int nrows,
+                            double* gtab, size_t gtab_set, int nset, hipStream_t st) {
   const size_t total = (size_t)nrows * S.N * S.N;
   if (nset < 1 || nset > 65535 || gtab_set < total * 2 || ctl_set < (size_t)nrows * cs) return hipErrorInvalidValue;
+  if (g0_set != 0 && g0_set < (size_t)2 * S.N * S.N) return hipErrorInvalidValue;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256), nset), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, ctl_set, gtab_set);
+  hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256), nset), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, ctl_set, gtab_set,
+                     g0_set);
+  return hipGetLastError();
+}
+
+hipError_t launch_ensemble_mean(const double* g, const double* reg, int nreg, const double* w, int nvar, int ndesign, int accumulate,
+                                double* mean, hipStream_t st) {
+  if (ndesign == 0) return hipSuccess;
+  if (nvar < 1 || nreg < 0 || (nreg > 0 && !reg)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_ensemble_mean, dim3((ndesign + 127) / 128), dim3(128), 0, st, g, reg, nreg, w, nvar, ndesign, accumulate, mean);
   return hipGetLastError();
 }
 

@@ -45,6 +45,9 @@ struct qd_optim {
   DBuf d_bx0, d_btgt, d_bpur, d_bjbar, d_brbib, d_bxbar;
   int batch_replicas = 0;    // sets the replicas hold
   int last_batch_sets = 0;   // qd_optim_last_batch_sets
+  // ensemble of system variants (qd_optim_evalGradF_ensemble): quadrature weights [nvar], the regularisation addends of the shared control
+  // vector [ENS_NREG][ndesign], the weighted mean of the gradients [ndesign]
+  DBuf d_ew, d_ereg, d_emean;
 };
 
 // ---- index helpers (src/util.cpp:150-278) ------------------------------------------------------
@@ -242,7 +245,7 @@ extern "C" void qd_optim_destroy(qd_optim* o) {
   (void)hipSetDevice(o->h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
   for (DBuf* b : {&o->d_x0, &o->d_tgt, &o->d_pur, &o->d_rbib, &o->d_jbar, &o->d_xbar, &o->d_w, &o->d_red}) b->release();
-  for (DBuf* b : {&o->d_bx0, &o->d_btgt, &o->d_bpur, &o->d_bjbar, &o->d_brbib, &o->d_bxbar}) b->release();
+  for (DBuf* b : {&o->d_bx0, &o->d_btgt, &o->d_bpur, &o->d_bjbar, &o->d_brbib, &o->d_bxbar, &o->d_ew, &o->d_ereg, &o->d_emean}) b->release();
   o->h_red.release();
   for (hipEvent_t e : o->evr)
     if (e) (void)hipEventDestroy(e);
@@ -476,7 +479,9 @@ static void finalize_J_diff(const qd_optim* o, double re, double im, double* rb,
 }
 
 // BSpline0::computeVariation(_diff) (src/controlbasis.cpp:257-312); every other basis returns 0
-static double control_variation(const qd_handle* h, const double* alpha, double* G, double var_bar) {
+// (terms: 1 = the differences, 2 = the boundary terms of enforce_bc, 3 = both.  Every element of G receives at most one addend of each
+//  kind, the difference first: a call with 1 followed by a call with 2 adds what one call with 3 adds, in the same order.)
+static double control_variation(const qd_handle* h, const double* alpha, double* G, double var_bar, int terms = 3) {
   double var = 0.0;
   const double fact = 2.0 * var_bar;
   for (int k = 0; k < h->S.Q; k++) {
@@ -495,7 +500,7 @@ static double control_variation(const qd_handle* h, const double* alpha, double*
             const double d = pr[base + lc] - pr[base + lc - 1];
             var += d * d;
           }
-          if (gr) {
+          if (gr && (terms & 1)) {
             gr[base] += fact * (pr[base] - pr[base + 1]);
             for (int lc = 1; lc < ns - 1; lc++) gr[base + lc] += fact * (2 * pr[base + lc] - pr[base + lc - 1] - pr[base + lc + 1]);
             gr[base + ns - 1] += fact * (pr[base + ns - 1] - pr[base + ns - 2]);
@@ -504,7 +509,7 @@ static double control_variation(const qd_handle* h, const double* alpha, double*
         if (h->dctl.enforce_bc) {
           const int b0 = g.skip + 2 * f * ns;
           var += pr[b0] * pr[b0] + pr[b0 + ns - 1] * pr[b0 + ns - 1] + pr[b0 + ns] * pr[b0 + ns] + pr[b0 + 2 * ns - 1] * pr[b0 + 2 * ns - 1];
-          if (gr) {
+          if (gr && (terms & 2)) {
             gr[b0] += fact * pr[b0];
             gr[b0 + ns - 1] += fact * pr[b0 + ns - 1];
             gr[b0 + ns] += fact * pr[b0 + ns];
@@ -1011,8 +1016,35 @@ struct BatchScope {
   }
 };
 
-static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mode, qd_objective_value* vals, double* grads, const char* who) {
-  if (!o || !vals || (grad_mode && !grads) || nset < 1 || (!alphas && o->h->ndesign > 0)) return fail(QD_ERR_INVALID, std::string(who) + ": null argument or nset < 1");
+// The sets of a batch_eval call as system variants of ONE control vector (qd_optim_evalF_ensemble / qd_optim_evalGradF_ensemble): the
+// caller has uploaded the variants' G0 (qd_handle::ensemble_upload, ens_g0) and replicated the control vector once per variant.
+constexpr int ENS_NREG = 3;  // regularisation addends per gradient element: Tikhonov, control variation, its boundary terms
+struct EnsembleCall {
+  const double* w;                   // quadrature weights [nvar]
+  const std::vector<double>* norms;  // Gershgorin row sum of every variant's Hsys
+  double* grad_mean;                 // [ndesign] (gradient mode): sum_j w[j] grads[j]
+};
+
+// the regularisation terms of a gradient, on the host (src/optimproblem.cpp:356-372)
+static void add_regularisation(const qd_optim* o, const double* alpha, double* grad) {
+  const int nd = o->h->ndesign;
+  for (int i = 0; i < nd; i++) grad[i] += o->gamma_tik * (alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]));
+  control_variation(o->h, alpha, grad, 0.5 * o->gamma_var);
+}
+
+// ... as the addends add_regularisation gives one element, in its order: reg [ENS_NREG][ndesign] (k_ensemble_mean adds them one by one)
+static void regularisation_addends(const qd_optim* o, const double* alpha, double* reg) {
+  const int nd = o->h->ndesign;
+  std::fill(reg, reg + (size_t)ENS_NREG * nd, 0.0);
+  for (int i = 0; i < nd; i++) reg[i] = o->gamma_tik * (alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]));
+  control_variation(o->h, alpha, reg + nd, 0.5 * o->gamma_var, 1);
+  control_variation(o->h, alpha, reg + 2 * (size_t)nd, 0.5 * o->gamma_var, 2);
+}
+
+// ens: null for a parameter-set batch.  An ensemble call may leave grads null (only the mean is wanted).
+static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mode, qd_objective_value* vals, double* grads, const char* who,
+                      const EnsembleCall* ens = nullptr) {
+  if (!o || !vals || (grad_mode && !grads && !ens) || nset < 1 || (!alphas && o->h->ndesign > 0)) return fail(QD_ERR_INVALID, std::string(who) + ": null argument or nset < 1");
   if (o->nranks != 1) return fail(QD_ERR_STATE, std::string(who) + ": single-rank entry point (the distributed form takes one control vector per call)");
   qd_handle* h = o->h;
   if (grad_mode && h->has_pipulse) return fail(QD_ERR_UNSUPPORTED, "qd_adjoint: derivative of pi-pulses is not implemented in the reference (src/oscillator.cpp:373-378)");
@@ -1053,8 +1085,17 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
     }
     if (concurrent) {
       DevTarget tgb = o->tg;
-      std::vector<double> sums((size_t)group * QD_NSUMS), rbib((size_t)group * 2 * nl);
+      std::vector<double> sums((size_t)group * QD_NSUMS), rbib((size_t)group * 2 * nl), reg;
       double applies = 0.0, fwd_ms = 0.0, adj_ms = 0.0;
+      const bool mean_dev = ens && grad_mode && nd > 0;  // the weighted mean of the gradients is formed on the device, group by group
+      if (mean_dev) {
+        if ((r = o->d_ew.ensure(nset)) || (r = o->d_ereg.ensure((size_t)ENS_NREG * nd)) || (r = o->d_emean.ensure(nd))) return r;
+        reg.resize((size_t)ENS_NREG * nd);
+        regularisation_addends(o, alphas, reg.data());
+        // (w and reg outlive the copies: the download of the mean synchronises before this scope ends)
+        QD_HIP(hipMemcpyAsync(o->d_ew.p, ens->w, sizeof(double) * nset, hipMemcpyHostToDevice, h->stream));
+        QD_HIP(hipMemcpyAsync(o->d_ereg.p, reg.data(), sizeof(double) * reg.size(), hipMemcpyHostToDevice, h->stream));
+      }
       for (int j0 = 0; j0 < nset; j0 += group) {
         const int g = std::min(group, nset - j0), nb = g * nl;
         h->sets = g;
@@ -1084,13 +1125,15 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
         QD_HIP(launch_seed(h->S, tgb, h->d_xT.p, o->d_brbib.p, nb, o->d_bxbar.p, h->stream));
         if ((r = h->adjoint_dev(o->d_bxbar.p, o->d_bjbar.p, nb, &tgb, false))) return r;  // (synchronises: rbib may be rewritten)
         adj_ms += h->last_adj_ms;
-        if ((r = h->batch_gradient(o->ebar, g, grads + (size_t)j0 * nd))) return r;
-        for (int s = 0; s < g; s++) {  // regularisation terms on the host, per set (src/optimproblem.cpp:356-372)
-          const double* alpha = alphas + (size_t)(j0 + s) * nd;
-          double* grad = grads + (size_t)(j0 + s) * nd;
-          for (int i = 0; i < nd; i++) grad[i] += o->gamma_tik * (alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]));
-          control_variation(h, alpha, grad, 0.5 * o->gamma_var);
-        }
+        if ((r = h->batch_gradient(o->ebar, g, grads ? grads + (size_t)j0 * nd : nullptr))) return r;
+        // the ensemble mean from the group's gradients where k_grad left them, accumulated over the groups in variant order
+        if (mean_dev) QD_HIP(launch_ensemble_mean(h->d_bgrad.p, o->d_ereg.p, ENS_NREG, o->d_ew.p + j0, g, nd, j0 > 0, o->d_emean.p, h->stream));
+        for (int s = 0; grads && s < g; s++)  // regularisation terms on the host, per set
+          add_regularisation(o, alphas + (size_t)(j0 + s) * nd, grads + (size_t)(j0 + s) * nd);
+      }
+      if (mean_dev) {
+        QD_HIP(hipMemcpyAsync(ens->grad_mean, o->d_emean.p, sizeof(double) * nd, hipMemcpyDeviceToHost, h->stream));
+        QD_HIP(hipStreamSynchronize(h->stream));
       }
       h->last_mean_applies = applies / nset;
       h->last_fwd_ms = fwd_ms;
@@ -1105,11 +1148,22 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
   }
   // fallback: set by set through the single evaluation - the same results, no launch shared
   double applies = 0.0;
+  std::vector<double> gone(ens && grad_mode && !grads ? nd : 0);
+  if (ens && grad_mode) std::fill(ens->grad_mean, ens->grad_mean + nd, 0.0);
   for (int j = 0; j < nset; j++) {
     const double* alpha = alphas + (size_t)j * nd;
-    r = grad_mode ? qd_optim_evalGradF(o, alpha, vals + j, grads + (size_t)j * nd) : qd_optim_evalF(o, alpha, vals + j);
+    double* grad = !grad_mode ? nullptr : grads ? grads + (size_t)j * nd : gone.data();
+    if (ens) {  // the handle as qd_set_hamiltonian would leave it for this variant: its G0, its row sum, the stand-in gates undecided
+      h->ens_g0 = h->d_eg0.p + (size_t)j * h->ens_g0_set();
+      h->dense_hsys_norm = (*ens->norms)[j];
+      h->sub_latch = -1;
+      h->params_dirty = true;
+    }
+    r = grad_mode ? qd_optim_evalGradF(o, alpha, vals + j, grad) : qd_optim_evalF(o, alpha, vals + j);
     if (r) return r;
     applies += h->last_mean_applies;
+    if (ens && grad_mode)  // (the arithmetic of k_ensemble_mean on the finished gradients)
+      for (int i = 0; i < nd; i++) ens->grad_mean[i] = std::fma(ens->w[j], grad[i], ens->grad_mean[i]);
   }
   h->last_mean_applies = applies / nset;
   h->batch_end();  // (the same state after the call on both paths: no stored trajectory, control table stale)
@@ -1125,6 +1179,74 @@ extern "C" int qd_optim_evalF_batch(qd_optim* o, const double* alphas, int nset,
 
 extern "C" int qd_optim_evalGradF_batch(qd_optim* o, const double* alphas, int nset, qd_objective_value* vals, double* grads) {
   return batch_eval(o, alphas, nset, true, vals, grads, "qd_optim_evalGradF_batch");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Ensemble of system variants (risk-neutral objective): ONE control vector on nvar systems that differ in Hsys, the weighted mean of
+// their objectives and gradients.  A user-Hamiltonian handle only: on the dense kernels every set of a launch reads a G(t) table of
+// its own, and a table does not care whether it differs from its neighbour through the controls or through Hsys - so this is
+// batch_eval with the control vector replicated once per variant (all sets' control tables come out identical) and k_gmat reading
+// set j's G0 from d_eg0 (qd_handle::batch_gtables).  One plan for all variants, from the largest row sum among them.  Where the batch
+// goes set by set, so does the ensemble: the handle is pointed at one variant after the other.
+// ---------------------------------------------------------------------------------------------------------------
+// leaves the handle on its own Hsys however the ensemble call ends
+struct EnsembleScope {
+  qd_handle* h;
+  double norm_saved;
+  int latch_saved;
+  explicit EnsembleScope(qd_handle* hh) : h(hh), norm_saved(hh->dense_hsys_norm), latch_saved(hh->sub_latch) {}
+  ~EnsembleScope() {
+    h->ens_g0 = nullptr;
+    h->dense_hsys_norm = norm_saved;
+    h->sub_latch = latch_saved;  // (the stand-in gates of the handle's own system: not what the variants' bounds decided)
+    h->params_dirty = true;
+    h->traj_valid = false;
+  }
+};
+
+static int ensemble_eval(qd_optim* o, const double* alpha, int nvar, const double* hsys_re, const double* hsys_im, const double* weights,
+                         bool grad_mode, qd_objective_value* vals, qd_objective_value* mean, double* grads, double* grad_mean, const char* who) {
+  if (!o || nvar < 1 || !hsys_re || !hsys_im || !mean || (grad_mode && !grad_mean) || (!alpha && o->h->ndesign > 0))
+    return fail(QD_ERR_INVALID, std::string(who) + ": null argument or nvar < 1");
+  if (o->nranks != 1) return fail(QD_ERR_STATE, std::string(who) + ": single-rank entry point");
+  qd_handle* h = o->h;
+  if (!h->S.dense) return fail(QD_ERR_STATE, std::string(who) + ": the handle needs qd_set_hamiltonian first (it supplies the control Hamiltonians Hc_k)");
+  std::vector<double> w(nvar, 1.0 / nvar);
+  if (weights) w.assign(weights, weights + nvar);
+  for (double wj : w)
+    if (!(wj >= 0.0) || !std::isfinite(wj)) return fail(QD_ERR_INVALID, std::string(who) + ": a weight is negative or not finite");
+  const int nd = h->ndesign;
+  int r;
+  std::vector<double> norms, alphas((size_t)nvar * nd);
+  std::vector<qd_objective_value> own(vals ? 0 : nvar);
+  if (!vals) vals = own.data();
+  for (int j = 0; j < nvar; j++) std::copy(alpha, alpha + nd, alphas.begin() + (size_t)j * nd);
+  EnsembleScope es(h);
+  if ((r = h->ensemble_upload(nvar, hsys_re, hsys_im, norms))) return r;
+  h->ens_g0 = h->d_eg0.p;
+  h->dense_hsys_norm = *std::max_element(norms.begin(), norms.end());  // (batch_begin and plan_sweep: row_bounds reads it)
+  h->sub_latch = -1;
+  const EnsembleCall ens{w.data(), &norms, grad_mean};
+  if ((r = batch_eval(o, alphas.data(), nvar, grad_mode, vals, grads, who, &ens))) return r;
+  double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = 0; j < nvar; j++) {
+    const double v[8] = {vals[j].objective, vals[j].cost, vals[j].regul, vals[j].penalty, vals[j].penalty_dpdm, vals[j].penalty_energy,
+                         vals[j].penalty_variation, vals[j].fidelity};
+    for (int k = 0; k < 8; k++) m[k] = std::fma(w[j], v[k], m[k]);
+  }
+  *mean = qd_objective_value{m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]};
+  return QD_OK;
+}
+
+extern "C" int qd_optim_evalF_ensemble(qd_optim* o, const double* alpha, int nvar, const double* hsys_re, const double* hsys_im,
+                                       const double* weights, qd_objective_value* vals, qd_objective_value* mean) {
+  return ensemble_eval(o, alpha, nvar, hsys_re, hsys_im, weights, false, vals, mean, nullptr, nullptr, "qd_optim_evalF_ensemble");
+}
+
+extern "C" int qd_optim_evalGradF_ensemble(qd_optim* o, const double* alpha, int nvar, const double* hsys_re, const double* hsys_im,
+                                           const double* weights, qd_objective_value* vals, qd_objective_value* mean, double* grads,
+                                           double* grad_mean) {
+  return ensemble_eval(o, alpha, nvar, hsys_re, hsys_im, weights, true, vals, mean, grads, grad_mean, "qd_optim_evalGradF_ensemble");
 }
 
 extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_batch_sets : QD_ERR_INVALID; }
