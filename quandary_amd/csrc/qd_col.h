@@ -49,6 +49,10 @@ static_assert(2 * KRY_MR + 4 <= GMRES_MR_G + 2, "slots of the global-memory Kryl
 constexpr int col_max_threads(int ept) { return ept == 5 ? 768 : 64 * ((64 + ept - 1) / ept); }
 
 __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double opaque(double v) {  // (qd_device.h: opaque(int))
+  asm volatile("" : "+v"(v));
+  return v;
+}
 
 // Ket class of a wave by the level i'_0 of oscillator 0 that all its columns share (USLOT): at the bottom level there is no ket-down
 // neighbour of oscillator 0, at the top level no ket-up neighbour and no T1 term.  KET_NONE: nothing known, every term is formed.
@@ -57,6 +61,11 @@ enum : int { KET_NONE = 0, KET_BOTTOM = 1, KET_INTERIOR = 2, KET_TOP = 3 };
 // slower on the 3 x 20 headline, 541.7 against 535.8 ms, profiles/ketedge_ab.txt: not the default)
 #ifndef QD_COL_KET_PERMUTE
 #define QD_COL_KET_PERMUTE 0
+#endif
+// Forward stage solve of the diagonal-split stationary solver without coupling in the frame where every drive coefficient is real
+// (ColTeam::stage, GAUGE): 1 = on; 0 (COLFLAGS) = the complex form everywhere, the code this file had before the form existed
+#ifndef QD_COL_GAUGE
+#define QD_COL_GAUGE 1
 #endif
 
 // SPLIT: the kernels of the diagonal-split solver keep (1 - alpha D)^-1 per element instead of the diagonal itself; the diagonal is then
@@ -313,10 +322,14 @@ struct ColLean {
   // NODIAG: only the off-diagonal part C = M - diag(M) (the diagonal-split solver applies the diagonal in closed form)
   // acc: added to the result (the accumulators start there: no extra instruction)
   // KC: ket class of the wave (forward NODIAG form only): the terms of oscillator 0 that the class does not have are not formed
-  template <bool TRANS, bool NODIAG = false, int KC = KET_NONE>
+  // RD: real drive (forward NODIAG form without coupling, on a vector in the rotated frame of ColTeam::stage): the coefficient of
+  // oscillator k is the real number c.q[k] (= alpha r_k there; c.p[k] is not read) on e + f - one sum of the four ladder neighbours
+  // and one fma per component instead of e, f and four: 10 fp64 instructions per oscillator and element instead of 16
+  template <bool TRANS, bool NODIAG = false, int KC = KET_NONE, bool RD = false>
   __device__ __forceinline__ double2 apply(const StepC<Q>& c, int j, const double2 own, const double2 prev, const double2 next,
                                            const double2* acc = nullptr) const {
     static_assert(KC == KET_NONE || (!TRANS && NODIAG && USLOT && !HJ && Q > 1), "class forms: the forward stage pass");
+    static_assert(!RD || (!TRANS && NODIAG && !HJ), "real drive: the forward stage pass without coupling");
     double ar = acc ? acc->x : 0.0, ai = acc ? acc->y : 0.0;
     if (!NODIAG) {
       double dwj, ddj;
@@ -329,20 +342,36 @@ struct ColLean {
       // oscillator 0 of a wave of known class (never the stride-1 oscillator): the bra neighbours, the ket neighbours there are, and
       // the T1 term with the coefficient set_alpha has formed whole
       const double2 xu = ld(aru[0] + (unsigned)j * COLB), xd = ld(ard[0] + (unsigned)j * COLB);
-      double er = su[0] * xu.x, ei = su[0] * xu.y;     // U1 - D2
-      double fr = -sd[0] * xd.x, fi = -sd[0] * xd.y;  // U2 - D1
-      if constexpr (KC != KET_BOTTOM) {
-        const double2 xdp = ld(tb + (unsigned)ocd[0][0] + (unsigned)j * COLB);
-        er = fma(-cy[0][0], xdp.x, er);
-        ei = fma(-cy[0][0], xdp.y, ei);
+      if constexpr (RD) {
+        double sr = fma(-sd[0], xd.x, su[0] * xu.x), si = fma(-sd[0], xd.y, su[0] * xu.y);  // e + f
+        if constexpr (KC != KET_BOTTOM) {
+          const double2 xdp = ld(tb + (unsigned)ocd[0][0] + (unsigned)j * COLB);
+          sr = fma(-cy[0][0], xdp.x, sr);
+          si = fma(-cy[0][0], xdp.y, si);
+        }
+        if constexpr (KC != KET_TOP) {
+          const double2 xup = ld(tb + (unsigned)ocu[0][0] + (unsigned)j * COLB);
+          sr = fma(cx[0][0], xup.x, sr);
+          si = fma(cx[0][0], xup.y, si);
+        }
+        ar = fma(c.q[0], sr, ar);
+        ai = fma(c.q[0], si, ai);
+      } else {
+        double er = su[0] * xu.x, ei = su[0] * xu.y;     // U1 - D2
+        double fr = -sd[0] * xd.x, fi = -sd[0] * xd.y;  // U2 - D1
+        if constexpr (KC != KET_BOTTOM) {
+          const double2 xdp = ld(tb + (unsigned)ocd[0][0] + (unsigned)j * COLB);
+          er = fma(-cy[0][0], xdp.x, er);
+          ei = fma(-cy[0][0], xdp.y, ei);
+        }
+        if constexpr (KC != KET_TOP) {
+          const double2 xup = ld(tb + (unsigned)ocu[0][0] + (unsigned)j * COLB);
+          fr = fma(cx[0][0], xup.x, fr);
+          fi = fma(cx[0][0], xup.y, fi);
+        }
+        ar = fma(c.q[0], er + fr, fma(c.p[0], ei - fi, ar));
+        ai = fma(c.q[0], ei + fi, fma(-c.p[0], er - fr, ai));
       }
-      if constexpr (KC != KET_TOP) {
-        const double2 xup = ld(tb + (unsigned)ocu[0][0] + (unsigned)j * COLB);
-        fr = fma(cx[0][0], xup.x, fr);
-        fi = fma(cx[0][0], xup.y, fi);
-      }
-      ar = fma(c.q[0], er + fr, fma(c.p[0], ei - fi, ar));
-      ai = fma(c.q[0], ei + fi, fma(-c.p[0], er - fr, ai));
       if constexpr (KC != KET_TOP) {  // T1 off-diagonal term (the top class has none)
         const double2 xl = ld(aru[0] + (unsigned)ocu[0][0] + (unsigned)j * COLB);
         ar = fma(g1u[0], xl.x, ar);
@@ -353,11 +382,18 @@ struct ColLean {
     for (int k = KC != KET_NONE ? 1 : 0; k < Q; k++) {
       double2 xu, xd, xup, xdp;
       nbrs(k, j, own, prev, next, xu, xd, xup, xdp);
-      const double er = fma(-cyv(j, k), xdp.x, su[k] * xu.x), ei = fma(-cyv(j, k), xdp.y, su[k] * xu.y);  // U1 - D2
-      const double fr = fma(cxv(j, k), xup.x, -sd[k] * xd.x), fi = fma(cxv(j, k), xup.y, -sd[k] * xd.y);  // U2 - D1
-      const double pk = TRANS ? -c.p[k] : c.p[k], qk = TRANS ? -c.q[k] : c.q[k];
-      ar = fma(qk, er + fr, fma(pk, ei - fi, ar));
-      ai = fma(qk, ei + fi, fma(-pk, er - fr, ai));
+      if constexpr (RD) {
+        const double sr = fma(cxv(j, k), xup.x, fma(-cyv(j, k), xdp.x, fma(-sd[k], xd.x, su[k] * xu.x)));  // e + f
+        const double si = fma(cxv(j, k), xup.y, fma(-cyv(j, k), xdp.y, fma(-sd[k], xd.y, su[k] * xu.y)));
+        ar = fma(c.q[k], sr, ar);
+        ai = fma(c.q[k], si, ai);
+      } else {
+        const double er = fma(-cyv(j, k), xdp.x, su[k] * xu.x), ei = fma(-cyv(j, k), xdp.y, su[k] * xu.y);  // U1 - D2
+        const double fr = fma(cxv(j, k), xup.x, -sd[k] * xd.x), fi = fma(cxv(j, k), xup.y, -sd[k] * xd.y);  // U2 - D1
+        const double pk = TRANS ? -c.p[k] : c.p[k], qk = TRANS ? -c.q[k] : c.q[k];
+        ar = fma(qk, er + fr, fma(pk, ei - fi, ar));
+        ai = fma(qk, ei + fi, fma(-pk, er - fr, ai));
+      }
       // T1 off-diagonal term: forward couples to (row + s, column + s), transposed to (row - s, column - s)
       double2 xl;
       if (k == L) {
@@ -426,6 +462,11 @@ struct ColTeam {
   typedef ColLean<Q, EPT, SPLIT, USLOT, HJ> ST;
   ST st;
   int kc;  // KCLS: the wave's ket class
+  // GAUGE: stage() solves in the frame where the drive is real (diagonal-split form without coupling)
+  static constexpr bool GAUGE = QD_COL_GAUGE && SPLIT && !HJ;
+  // its LDS: one 16-byte word per thread behind the column table, where the thread parks its row phasor during the solve
+  static __host__ __device__ unsigned gauge_off(int N) { return ST::tab_off(N) + 48u * (unsigned)ST::ncols(N); }
+  static __host__ __device__ size_t gauge_lds_extra(int threads) { return GAUGE ? 16 * (size_t)threads : 0; }
   double* red;
   float4* fred;  // two slots of 16 partial sums of the solver's fp32 norm reduction
   int redslot, nw;
@@ -678,12 +719,58 @@ struct ColTeam {
   // the diagonal of M has a non-positive real part) taken from the first pass - never looser than the rule it stands for.
   // SPLIT: the step size is folded into the coefficients (set_alpha<false, true> has scaled the thread's part): a pass forms
   // x + alpha C z with its accumulators started at x - two fp64 instructions per element less.
-  __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, const double2 (&x)[EPT], double2 (&z)[EPT]) {
+  //
+  // GAUGE (SPLIT without coupling): the solve runs in the frame where the drive of every oscillator is real.  With the sub-step's
+  // c_k = q_k + i p_k = r_k e^{i theta_k} and the diagonal unitary U = (x)_k exp(-i theta_k n_k), rho~ = U rho U^dag is
+  // rho~_ij = w_i conj(w_j) rho_ij, w_i = prod_k u_k^{i_k}, u_k = conj(c_k) / r_k.  In M rho the drive of oscillator k is
+  // conj(c_k) E + c_k F with E the two neighbours whose i_k - j_k is one larger and F the two where it is one smaller: their phasors
+  // differ from the element's own by conj(u_k) and u_k, so in the rotated frame the term is r_k (E~ + F~) (ColLean::apply, RD).
+  // The diagonal - hence P - and the T1 term, which couples (i + 1, j + 1) to (i, j), do not change; the rotation is elementwise and
+  // unitary, so iterate m of the rotated solve is U z_m U^dag and the update norms are the ones of the lab frame up to rounding: same
+  // stopping rule, same pass counts.  The controls are constant within a sub-step, so this is exact for any phase jump between
+  // sub-steps.  Per sub-step every wave forms the row phasors w_i (lane i; binary powering on the level indices, |w| renormalised
+  // once) - the column phasors of its slots are lanes of the same register - rotates x in, and after the solve rotates out; the
+  // element phasors are formed again there from the row phasor parked in LDS, not kept in registers across the pass loop.  For these
+  // forms stage() also makes the step: on exit x = x_{n+1} = U^dag (2 z~ - x~) U, and z = U^dag z~ U where the stages are stored
+  // (A.ztraj); the caller neither publishes x nor combines.  Everything outside sees lab-frame values only, and a sub-step stays a
+  // function of the lab state and the control row: sliced, chunked and batched sweeps keep their bits.
+  // r_k^2 below 1e-280 counts as no drive (u_k = 1, r_k = 0): never a NaN.
+  __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, double2 (&x)[EPT], double2 (&z)[EPT]) {
     double sc = A.inv_abs2 / (alpha * alpha);
     if constexpr (KCLS) sc = to_scalar(sc);  // (wave-uniform: a scalar operand of the tested passes instead of a register pair of every pass)
     StepC<Q> ca = c;  // (alpha p, alpha q, alpha cs, alpha sn: scaled in VALU once per sub-step, back to scalar registers)
+    if constexpr (GAUGE) {
+      double2 w = make_double2(1.0, 0.0);
 #pragma unroll
-    for (int k = 0; k < (SPLIT ? Q : 0); k++) {
+      for (int k = 0; k < Q; k++) {
+        const double r2 = fma(c.p[k], c.p[k], c.q[k] * c.q[k]);
+        const bool on = r2 > 1e-280;
+        const double ir = rsqrt_nr(on ? r2 : 1.0);
+        ca.q[k] = to_scalar(on ? alpha * (r2 * ir) : 0.0);  // alpha r_k
+        double2 pw = on ? make_double2(c.q[k] * ir, -c.p[k] * ir) : make_double2(1.0, 0.0);  // u_k^(2^b)
+        // the row's level index i_k from sd = sqrt(i_k) (0 on the padding rows), re-derived here: hoisted out of the time loop it
+        // is one more register across the pass loop
+        const double sdk = opaque(st.sd[k]);
+        const int e = (int)fma(sdk, sdk, 0.5);
+        const int n = A.S.n[k];
+        for (int b = 1; b < n; b <<= 1) {
+          if (e & b) w = make_double2(fma(w.x, pw.x, -w.y * pw.y), fma(w.x, pw.y, w.y * pw.x));
+          pw = make_double2(fma(pw.x, pw.x, -pw.y * pw.y), 2.0 * pw.x * pw.y);
+        }
+      }
+      const double nr = fma(-0.5, fma(w.x, w.x, w.y * w.y), 1.5);  // 1 / |w| to second order: |w| = 1 to a few ulp
+      w = make_double2(w.x * nr, w.y * nr);
+      st.st(gauge_slot(), w);
+#pragma unroll
+      for (int j = 0; j < EPT; j++) {
+        const double2 f = phasor(w, j), v = x[j];
+        x[j] = make_double2(fma(f.x, v.x, -f.y * v.y), fma(f.x, v.y, f.y * v.x));  // x~ = f x
+        slot_fence_pin<EPT>(x[j]);  // (one slot's phasor at a time)
+      }
+      publish(x);
+    }
+#pragma unroll
+    for (int k = 0; k < (SPLIT && !GAUGE ? Q : 0); k++) {
       ca.p[k] = to_scalar(alpha * c.p[k]);
       ca.q[k] = to_scalar(alpha * c.q[k]);
     }
@@ -709,7 +796,32 @@ struct ColTeam {
       iter = passes<KET_NONE>(A, ca, alpha, sc, skip, rel2, thr, d0, dprev, x, z);
     }
     if (SKIP) lastn = iter + 1;
+    if constexpr (GAUGE) {
+      const double2 w = st.ld(gauge_slot());
+      const bool stages = A.ztraj != nullptr;
+#pragma unroll
+      for (int j = 0; j < EPT; j++) {
+        const double2 f = phasor(w, j);
+        const double tx = fma(2.0, z[j].x, -x[j].x), ty = fma(2.0, z[j].y, -x[j].y);
+        x[j] = make_double2(fma(f.x, tx, f.y * ty), fma(f.x, ty, -f.y * tx));  // conj(f) (2 z~ - x~)
+        if (stages) z[j] = make_double2(fma(f.x, z[j].x, f.y * z[j].y), fma(f.x, z[j].y, -f.y * z[j].x));
+        slot_fence_pin<EPT>(x[j]);
+      }
+    }
     return iter + 1;
+  }
+  // GAUGE: LDS byte address of the thread's parked row phasor, from the wave's column block and the lane id - nothing of it is held in a
+  // vector register across the pass loop
+  __device__ __forceinline__ unsigned gauge_slot() const {
+    return gauge_off(st.N) + (unsigned)(st.col0 / EPT) * 1024u + __lane_id() * 16u;
+  }
+  // GAUGE: phasor w_row conj(w_col) of the thread's element in slot j; w = the row phasors, one per lane - the one of column col0 + j
+  // is lane col0 + j of the same register (idle columns and padding rows: 1)
+  __device__ __forceinline__ double2 phasor(const double2 w, int j) const {
+    const int lc = st.col0 + j;
+    const double cr = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(w.x), lc), __builtin_amdgcn_readlane(__double2loint(w.x), lc));
+    const double ci = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(w.y), lc), __builtin_amdgcn_readlane(__double2loint(w.y), lc));
+    return make_double2(fma(w.x, cr, w.y * ci), fma(w.y, cr, -w.x * ci));
   }
   // the pass loop of stage() in the form of ket class KC (ColLean::apply), on stage()'s own variables; returns the index of the last pass
   template <int KC>
@@ -725,7 +837,7 @@ struct ColTeam {
         const double2 own = z[j];
         double2 w;
         if constexpr (SPLIT) {
-          w = st.template apply<false, true, KC>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j], &x[j]);  // x + alpha C z
+          w = st.template apply<false, true, KC, GAUGE>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j], &x[j]);  // x + alpha C z
         } else {
           const double2 t = st.template apply<false, false>(c, j, own, prev, z[j + 1 < EPT ? j + 1 : j]);
           w.x = fma(alpha, t.x, x[j].x);
@@ -1257,7 +1369,11 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
     if (SPLIT) tm.template set_alpha<false, SPLIT && !KRY>(S, 0.5 * c.h);
     if (A.traj) store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, x, true);
     // the sub-step in stage form (ColTeam::stage): x is the right-hand side of the solve and stays in registers
-    tm.publish(x);
+    // (GAUGE: stage() publishes the rotated x itself, and returns with the step made)
+    constexpr bool GAUGE = TM::GAUGE && !KRY;
+    if constexpr (!GAUGE) tm.publish(x);
+    // (GAUGE: on return x is x_{n+1} already, and z is the lab-frame stage ONLY where stages are stored (A.ztraj) - otherwise it is left in
+    //  the rotated frame of this sub-step and must not be read; the stage store below is its one consumer)
     double2 z[EPT];
     if constexpr (KRY) napply += tm.kry_stage(A, c, 0.5 * c.h, x, z);
     else napply += tm.stage(A, c, 0.5 * c.h, x, z);
@@ -1272,7 +1388,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
         }
     }
 #pragma unroll
-    for (int j = 0; j < EPT; j++) {  // x_{n+1} = x + h k = 2 z - x
+    for (int j = 0; j < (GAUGE ? 0 : EPT); j++) {  // x_{n+1} = x + h k = 2 z - x
       x[j].x = fma(2.0, z[j].x, -x[j].x);
       x[j].y = fma(2.0, z[j].y, -x[j].y);
     }
@@ -1307,7 +1423,12 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
               pen_local += (A.tg.objective_type == QD_OBJ_JTRACE ? -1.0 : 1.0) * weight * A.dt * jr;
             }
         }
-        if (A.tg.objective_type == QD_OBJ_JTRACE) pen_uniform += weight * A.dt;
+        // (GAUGE: the uniform part of the Jtrace penalty is added by the owner of element (0, 0) to its local sum - an accumulator of
+        //  its own is one more register pair across the pass loop, and spilt)
+        if (A.tg.objective_type == QD_OBJ_JTRACE) {
+          if constexpr (GAUGE) pen_local += (tm.st.row == 0 && tm.st.colof(0) == 0) ? weight * A.dt : 0.0;
+          else pen_uniform += weight * A.dt;
+        }
       }
       if (leak) {
 #pragma unroll
@@ -1546,8 +1667,10 @@ static int col_grid(K kern, const SweepArgs& a, int threads, size_t lds) {
 template <int Q, int EPT, bool SPLIT, bool USLOT, bool SKIP, bool KRY>
 static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
-  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0);
   const int threads = 64 * (ST::ncols(a.S.N) / EPT);
+  // (the forward stage solve in the rotated frame parks one phasor per thread: ColTeam::stage, GAUGE)
+  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N)
+                                                 : adjoint ? 0 : ColTeam<Q, EPT, SPLIT, USLOT, SKIP, QD_COL_HJ>::gauge_lds_extra(threads));
   auto kf = adjoint ? QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY> : QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
