@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "qd_device.h"
+#include "qd_gauge.h"
 
 // With QD_COL_SETS 1 (set by qd_col_sets.hip / qd_colj_sets.hip before the include, objects of their own): the SETS form of the
 // stationary-iteration sweeps, k_*_col_sets / k_*_colj_sets - the same templates, compiled a second time.  The task of initial condition
@@ -29,8 +30,10 @@
 #endif
 #if QD_COL_SETS
 #define QD_COL_CTL(A, ic) (A.ctl + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * A.ctl_set)
+#define QD_COL_GAUGE_TAB(A, ic) (gauge_tab(A) + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * gauge_set(A))
 #else
 #define QD_COL_CTL(A, ic) A.ctl
+#define QD_COL_GAUGE_TAB(A, ic) gauge_tab(A)
 #endif
 
 namespace qd {
@@ -49,10 +52,6 @@ static_assert(2 * KRY_MR + 4 <= GMRES_MR_G + 2, "slots of the global-memory Kryl
 constexpr int col_max_threads(int ept) { return ept == 5 ? 768 : 64 * ((64 + ept - 1) / ept); }
 
 __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ double opaque(double v) {  // (qd_device.h: opaque(int))
-  asm volatile("" : "+v"(v));
-  return v;
-}
 
 // Ket class of a wave by the level i'_0 of oscillator 0 that all its columns share (USLOT): at the bottom level there is no ket-down
 // neighbour of oscillator 0, at the top level no ket-up neighbour and no T1 term.  KET_NONE: nothing known, every term is formed.
@@ -66,6 +65,12 @@ enum : int { KET_NONE = 0, KET_BOTTOM = 1, KET_INTERIOR = 2, KET_TOP = 3 };
 // (ColTeam::stage, GAUGE): 1 = on; 0 (COLFLAGS) = the complex form everywhere, the code this file had before the form existed
 #ifndef QD_COL_GAUGE
 #define QD_COL_GAUGE 1
+#endif
+// Where that form issues the load of a sub-step's row phasor from the phasor table (qd_gauge.h; k_forward): 0 = at the top of the
+// sub-step, beside the scalar loads of its control row, consumed at the rotation in; 1 = the NEXT sub-step's right behind the pass loop,
+// covered by the rotation out and the penalty block (four registers live across the step tail, never across the pass loop)
+#ifndef QD_COL_GAUGE_AHEAD
+#define QD_COL_GAUGE_AHEAD 0
 #endif
 
 // SPLIT: the kernels of the diagonal-split solver keep (1 - alpha D)^-1 per element instead of the diagonal itself; the diagonal is then
@@ -706,6 +711,21 @@ struct ColTeam {
     return iter;
   }
 
+  // GAUGE: what a sub-step reads from the phasor table (qd_gauge.h), row = the table row of the sub-step: r_k through the scalar path
+  // like the control row (load_step_k), the thread's row phasor as one 16-byte load - lane = row of rho; the padding rows hold 1
+  struct GaugeRow {
+    double r[Q];
+    double2 w;
+  };
+  static __device__ __forceinline__ void gauge_load_r(const double* row, GaugeRow& g) {
+#pragma unroll
+    for (int k = 0; k < Q; k++) g.r[k] = kload(row + GAUGE_R + k);
+  }
+  static __device__ __forceinline__ double2 gauge_load_w(const double* row) {
+    const col_d2 t = *(reinterpret_cast<const col_d2*>(row) + __lane_id());
+    return make_double2(t.x, t.y);
+  }
+
   // Forward sub-step in STAGE form.  The reference solves (I - alpha M) k = M x and sets x += h k (ImplMidpoint::evolveFWD,
   // timestepper.cpp:594-629, alpha = h / 2).  The iterates of its Neumann solver, y_0 = b = M x, y_{m+1} = b + alpha M y_m (SPLIT:
   // y_0 = P b, y_{m+1} = P (b + alpha C y_m), P = (1 - alpha D)^-1, C = M - D), map one to one onto iterates of the stage
@@ -728,38 +748,25 @@ struct ColTeam {
   // The diagonal - hence P - and the T1 term, which couples (i + 1, j + 1) to (i, j), do not change; the rotation is elementwise and
   // unitary, so iterate m of the rotated solve is U z_m U^dag and the update norms are the ones of the lab frame up to rounding: same
   // stopping rule, same pass counts.  The controls are constant within a sub-step, so this is exact for any phase jump between
-  // sub-steps.  Per sub-step every wave forms the row phasors w_i (lane i; binary powering on the level indices, |w| renormalised
-  // once) - the column phasors of its slots are lanes of the same register - rotates x in, and after the solve rotates out; the
+  // sub-steps.  r_k and the row phasors w_i depend on the control row and the row index only: they come from the phasor table built
+  // with the control table (qd_gauge.h, k_gauge; lane i reads w_i) - the column phasors of a wave's slots are lanes of the same
+  // register.  Per sub-step every wave rotates x in, and after the solve rotates out; the
   // element phasors are formed again there from the row phasor parked in LDS, not kept in registers across the pass loop.  For these
   // forms stage() also makes the step: on exit x = x_{n+1} = U^dag (2 z~ - x~) U, and z = U^dag z~ U where the stages are stored
   // (A.ztraj); the caller neither publishes x nor combines.  Everything outside sees lab-frame values only, and a sub-step stays a
   // function of the lab state and the control row: sliced, chunked and batched sweeps keep their bits.
-  // r_k^2 below 1e-280 counts as no drive (u_k = 1, r_k = 0): never a NaN.
-  __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, double2 (&x)[EPT], double2 (&z)[EPT]) {
+  // r_k^2 below 1e-280 counts as no drive (u_k = 1, r_k = 0: gauge_osc of qd_gauge.h): never a NaN.
+  // g: r_k and the thread's row phasor of this sub-step, from the phasor table (gauge_load_r / gauge_load_w); gnext: where stage() is to
+  // fetch the next sub-step's row phasor into g.w behind the pass loop (QD_COL_GAUGE_AHEAD), or null.  Both unused without GAUGE.
+  __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, double2 (&x)[EPT], double2 (&z)[EPT], GaugeRow& g,
+                                       const double* gnext) {
     double sc = A.inv_abs2 / (alpha * alpha);
     if constexpr (KCLS) sc = to_scalar(sc);  // (wave-uniform: a scalar operand of the tested passes instead of a register pair of every pass)
     StepC<Q> ca = c;  // (alpha p, alpha q, alpha cs, alpha sn: scaled in VALU once per sub-step, back to scalar registers)
     if constexpr (GAUGE) {
-      double2 w = make_double2(1.0, 0.0);
 #pragma unroll
-      for (int k = 0; k < Q; k++) {
-        const double r2 = fma(c.p[k], c.p[k], c.q[k] * c.q[k]);
-        const bool on = r2 > 1e-280;
-        const double ir = rsqrt_nr(on ? r2 : 1.0);
-        ca.q[k] = to_scalar(on ? alpha * (r2 * ir) : 0.0);  // alpha r_k
-        double2 pw = on ? make_double2(c.q[k] * ir, -c.p[k] * ir) : make_double2(1.0, 0.0);  // u_k^(2^b)
-        // the row's level index i_k from sd = sqrt(i_k) (0 on the padding rows), re-derived here: hoisted out of the time loop it
-        // is one more register across the pass loop
-        const double sdk = opaque(st.sd[k]);
-        const int e = (int)fma(sdk, sdk, 0.5);
-        const int n = A.S.n[k];
-        for (int b = 1; b < n; b <<= 1) {
-          if (e & b) w = make_double2(fma(w.x, pw.x, -w.y * pw.y), fma(w.x, pw.y, w.y * pw.x));
-          pw = make_double2(fma(pw.x, pw.x, -pw.y * pw.y), 2.0 * pw.x * pw.y);
-        }
-      }
-      const double nr = fma(-0.5, fma(w.x, w.x, w.y * w.y), 1.5);  // 1 / |w| to second order: |w| = 1 to a few ulp
-      w = make_double2(w.x * nr, w.y * nr);
+      for (int k = 0; k < Q; k++) ca.q[k] = to_scalar(fma(alpha, g.r[k], 0.0));  // alpha r_k (a silent oscillator: + 0.0, also under alpha < 0)
+      const double2 w = g.w;
       st.st(gauge_slot(), w);
 #pragma unroll
       for (int j = 0; j < EPT; j++) {
@@ -797,6 +804,7 @@ struct ColTeam {
     }
     if (SKIP) lastn = iter + 1;
     if constexpr (GAUGE) {
+      if (QD_COL_GAUGE_AHEAD && gnext) g.w = gauge_load_w(gnext);
       const double2 w = st.ld(gauge_slot());
       const bool stages = A.ztraj != nullptr;
 #pragma unroll
@@ -1363,20 +1371,28 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
     }
   };
 
+  // (GAUGE: stage() solves in the real-drive frame; r_k and the thread's row phasor of a sub-step come from row s of the phasor table)
+  constexpr bool GAUGE = TM::GAUGE && !KRY;
+  typename TM::GaugeRow grow;
+  const double* gtab = GAUGE ? QD_COL_GAUGE_TAB(A, ic) : nullptr;
+  if constexpr (GAUGE && QD_COL_GAUGE_AHEAD) grow.w = TM::gauge_load_w(gtab + (size_t)s_lo * GAUGE_STRIDE);
   for (int s = s_lo; s < s_hi; s++) {
     StepC<Q> c;
     load_step_k<Q>(QD_COL_CTL(A, ic) + (size_t)s * A.cs, c, HJ);
+    if constexpr (GAUGE) {
+      TM::gauge_load_r(gtab + (size_t)s * GAUGE_STRIDE, grow);
+      if constexpr (!QD_COL_GAUGE_AHEAD) grow.w = TM::gauge_load_w(gtab + (size_t)s * GAUGE_STRIDE);
+    }
     if (SPLIT) tm.template set_alpha<false, SPLIT && !KRY>(S, 0.5 * c.h);
     if (A.traj) store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, x, true);
     // the sub-step in stage form (ColTeam::stage): x is the right-hand side of the solve and stays in registers
     // (GAUGE: stage() publishes the rotated x itself, and returns with the step made)
-    constexpr bool GAUGE = TM::GAUGE && !KRY;
     if constexpr (!GAUGE) tm.publish(x);
     // (GAUGE: on return x is x_{n+1} already, and z is the lab-frame stage ONLY where stages are stored (A.ztraj) - otherwise it is left in
     //  the rotated frame of this sub-step and must not be read; the stage store below is its one consumer)
     double2 z[EPT];
     if constexpr (KRY) napply += tm.kry_stage(A, c, 0.5 * c.h, x, z);
-    else napply += tm.stage(A, c, 0.5 * c.h, x, z);
+    else napply += tm.stage(A, c, 0.5 * c.h, x, z, grow, GAUGE && QD_COL_GAUGE_AHEAD && s + 1 < s_hi ? gtab + (size_t)(s + 1) * GAUGE_STRIDE : nullptr);
     if (A.ztraj && tm.st.rowok) {  // the primal stage, read back by the adjoint sweep instead of repeating this solve: private to
       // this kernel pair, kept interleaved (one 16-byte streaming access per element; qd_handle tags the layout: ztraj_fmt)
       col_d2* dst = reinterpret_cast<col_d2*>(A.ztraj) + ((size_t)s * A.nb + ic) * dim;

@@ -77,7 +77,7 @@ extern "C" void qd_destroy(qd_handle* h) {
   h->h_bgrad.release();
   for (DBuf* b : {&h->d_params, &h->d_tbar, &h->d_tred, &h->d_sched_t, &h->d_sched_h, &h->d_etimes, &h->d_ezero, &h->d_table, &h->d_etable, &h->d_onerow,
                   &h->d_onetime, &h->d_tstates, &h->d_purity, &h->d_x0, &h->d_xT, &h->d_traj, &h->d_ztraj, &h->d_res,
-                  &h->d_xbar, &h->d_jbar, &h->d_coeff, &h->d_coeffsum, &h->d_grad, &h->d_y, &h->d_sched, &h->d_stash, &h->d_kry, &h->d_ecoef, &h->d_edig, &h->d_work, &h->d_g0, &h->d_hcr, &h->d_hci, &h->d_gtab, &h->d_gone})
+                  &h->d_xbar, &h->d_jbar, &h->d_coeff, &h->d_coeffsum, &h->d_grad, &h->d_y, &h->d_sched, &h->d_stash, &h->d_kry, &h->d_ecoef, &h->d_edig, &h->d_work, &h->d_g0, &h->d_hcr, &h->d_hci, &h->d_gtab, &h->d_gone, &h->d_gauge})
     b->release();
   if (h->d_segs) (void)hipFree(h->d_segs);
   if (h->d_oscs) (void)hipFree(h->d_oscs);
@@ -467,9 +467,30 @@ int qd_handle::refresh_tables() {
     S.gtab = d_gtab.p;
     QD_HIP(launch_gmat(S, ens_g0 ? ens_g0 : d_g0.p, d_table.p, cs, (int)sched_t.size(), d_gtab.p, stream));
   }
+  gauge_valid = false;  // r_k and the row phasors of every table row, for the lean column forward sweeps (qd_gauge.h)
+  if (gauge_wanted()) {
+    int r;
+    if ((r = gauge_table())) return r;
+  }
   // asynchronous: complete at the stream synchronisation that ends the sweep (forward_dev)
   QD_HIP(hipMemcpyAsync(h_etable.p, d_etable.p, sizeof(double) * etimes.size() * cs, hipMemcpyDeviceToHost, stream));
   params_dirty = false;
+  return QD_OK;
+}
+
+// The handle's plan can select a lean column forward kernel that solves in the real-drive frame (ColTeam::GAUGE of qd_col.h: the
+// diagonal-split solver, no coupling): every condition of col_sweep that no option and no control vector decides.
+bool qd_handle::gauge_wanted() const {
+  return precision == QD_PRECISION_F64 && collean_available(S, opts) && !S.hasJ && sol.stepper != QD_STEPPER_EE;
+}
+
+// the phasor table of the current control table, behind it on the stream
+int qd_handle::gauge_table() {
+  if (gauge_valid) return QD_OK;
+  int r;
+  if ((r = d_gauge.ensure(sched_t.size() * (size_t)GAUGE_STRIDE))) return r;
+  QD_HIP(launch_gauge(S, d_table.p, cs, (int)sched_t.size(), d_gauge.p, stream));
+  gauge_valid = true;
   return QD_OK;
 }
 
@@ -536,10 +557,17 @@ int qd_handle::batch_begin(const double* alphas, int nset) {
 // has written - k_gmat with the sets on grid.y, the arithmetic of refresh_tables element by element.  Per group of sets, so that the
 // tables in memory are those of the launches that read them.
 int qd_handle::batch_gtables(int first, int nsets) {
-  if (!S.dense) return QD_OK;
+  if (!batch_gtab_set()) return QD_OK;
   QD_HIP(qd::use_device(device));
   int r;
   if ((r = d_bgtab.ensure((size_t)nsets * batch_gtab_set()))) return r;
+  if (!S.dense) {  // the lean column systems: every set's phasor table (qd_gauge.h), the arithmetic of gauge_table
+    QD_HIP(launch_gauge_sets(S, d_btable.p + (size_t)first * batch_ctl_set(), batch_ctl_set(), cs, (int)sched_t.size(), d_bgtab.p,
+                             batch_gtab_set(), nsets, stream));
+    bgtab_first = first;
+    bgtab_sets = nsets;
+    return QD_OK;
+  }
   // (an ensemble of system variants: set j of the call reads its own G0, ensemble_upload)
   const double* g0 = ens_g0 ? ens_g0 + (size_t)first * ens_g0_set() : d_g0.p;
   QD_HIP(launch_gmat_sets(S, g0, ens_g0 ? ens_g0_set() : 0, d_btable.p + (size_t)first * batch_ctl_set(), batch_ctl_set(), cs,
@@ -1029,6 +1057,17 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
       return fail(QD_ERR_STATE, "parameter-set batch on a user Hamiltonian: the G(t) tables of the sets being swept have not been built (qd_handle::batch_gtables), or one table exceeds the 32-bit set stride");
     a.S.gtab = h->d_bgtab.p;
     a.gtab_set = (unsigned)h->batch_gtab_set();
+  }
+  if (p.family == Family::Col && !S.hasJ) {  // the phasor table the forward kernels of the real-drive frame read (qd_gauge.h)
+    int rg;
+    if (sets) {  // the group's tables, one per set
+      if (!batch_gtab_set() || bgtab_first != batch_first || bgtab_sets < sets || batch_gtab_set() > 0xffffffffull)
+        return fail(QD_ERR_STATE, "parameter-set batch on the lean column kernels: the phasor tables of the sets being swept have not been built (qd_handle::batch_gtables), or one table exceeds the 32-bit set stride");
+      set_gauge_tab(a, d_bgtab.p, (unsigned)batch_gtab_set());
+    } else {
+      if ((rg = gauge_table())) return rg;
+      set_gauge_tab(a, d_gauge.p, 0u);
+    }
   }
   a.cs = h->cs;
   a.nsub = h->nsub;

@@ -8,6 +8,7 @@
 
 #include <rccl/rccl.h>
 
+#include "qd_gauge.h"
 #include "qd_internal.h"
 
 #define QD_HIP(expr)                                                                                   \
@@ -179,6 +180,15 @@ struct qd_handle {
   int arm_slices(qd::SweepArgs& a, int nb, int which);
   int ensure_big(int nb);            // no-op unless the launch configuration is the large-state variant
   qd::DBuf d_g0, d_hcr, d_hci, d_gtab, d_gone;  // dense user-Hamiltonian path (qd_set_hamiltonian)
+  // Phasor table of the real-drive frame (qd_gauge.h), one row per row of d_table: what the lean column forward kernels of the
+  // diagonal-split solver without coupling read in place of forming r_k and the row phasors per wave and sub-step.  gauge_wanted: the
+  // handle's plan can select such a kernel - whatever neumann_split says now, the option may change after qd_create; refresh_tables
+  // then builds the table with the control table.  prepare_sweep builds it for a lean column sweep that finds it stale all the same
+  // (an option that admits the family only later).  gauge_valid: d_gauge belongs to the current d_table.
+  qd::DBuf d_gauge;
+  bool gauge_valid = false;
+  bool gauge_wanted() const;
+  int gauge_table();
   // infinity norms of the uploaded Hamiltonians (row_bounds: the standard-model constants say nothing about a user Hamiltonian)
   double dense_hsys_norm = 0.0;
   std::vector<double> dense_hc_norm;  // per oscillator: ||Re Hc_k||_inf + ||Im Hc_k||_inf
@@ -241,8 +251,12 @@ struct qd_handle {
   // handle's own d_gtab and S.gtab are left alone like d_table)
   qd::DBuf d_bgtab;
   int bgtab_first = 0, bgtab_sets = 0;  // the sets whose tables d_bgtab holds (0 sets = none)
-  size_t batch_gtab_set() const { return S.dense ? sched_t.size() * (size_t)S.N * S.N * 2 : 0; }  // the rows of batch_ctl_set() x N^2 complex
-  int batch_gtables(int first, int nsets);  // G(t) tables of the sets [first, first + nsets) from their control tables, one launch
+  // (the lean column systems, which are never dense: the group's phasor tables in the same buffer under the same bookkeeping, one per
+  // set, rows x GAUGE_STRIDE doubles apart - memory that lies beside the trajectory and is weighed with it the same way)
+  size_t batch_gtab_set() const {  // the rows of batch_ctl_set() x N^2 complex
+    return S.dense ? sched_t.size() * (size_t)S.N * S.N * 2 : gauge_wanted() ? sched_t.size() * (size_t)qd::GAUGE_STRIDE : 0;
+  }
+  int batch_gtables(int first, int nsets);  // G(t) / phasor tables of the sets [first, first + nsets) from their control tables, one launch
   qd::HBuf h_bparams, h_betable, h_bgrad;
   // ensemble of system variants (qd_optim_evalF_ensemble / qd_optim_evalGradF_ensemble): one control vector, nvar matrices Hsys.  d_eg0
   // holds their G0 = -i Hsys, ens_g0_set() doubles apart.  While ens_g0 is set the G(t) tables are built from it instead of d_g0: set j of

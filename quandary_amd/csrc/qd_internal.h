@@ -28,6 +28,7 @@ struct DevSys {
   const double* hcr;   // [Q][N*N] Re(Hc_k), row-major
   const double* hci;   // [Q][N*N] Im(Hc_k)
   const double* gtab;  // [rows][N*N] interleaved complex: G(t_row) = -i H(t_row), one row per control-table row
+                       // (matrix-free systems on the lean column kernels, never dense: their phasor table, through gauge_tab() of qd_gauge.h only)
   // states beyond one CU's LDS (dim > 4096, qd_big.h): per-element invariants and the per-state work vectors in global memory
   const double* ecoef;   // [dim] (Delta, d)
   const unsigned* edig;  // [dim] (packed bra digits, packed ket digits)
@@ -135,6 +136,7 @@ struct SweepArgs {
   int col_noskip;  // lean column kernels: test the stopping rule in every pass (option col_skip = 0)
   // parameter-set batch of a dense user Hamiltonian: doubles between two sets' G(t) tables = (rows of one table) x N^2 x 2, S.gtab being
   // the first set's (sweep_gtab<SETS>, qd_device.h; in what was padding behind col_noskip, like nb_set and ctl_set)
+  // (lean column kernels: the doubles between two sets' phasor tables, through gauge_set() of qd_gauge.h only)
   unsigned gtab_set;
   unsigned long long sched_ticks;  // wall_clock64 ticks (100 MHz) a slice may wait for its predecessor before the error word is raised
   double* stash;        // [2][nb][2*dim] staging area of the several-elements-per-thread variants (adjoint state / midpoint state

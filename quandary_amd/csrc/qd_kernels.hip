@@ -18,6 +18,7 @@
 
 #include "qd_device.h"
 #include "qd_big.h"
+#include "qd_gauge.h"
 
 namespace qd {
 
@@ -442,6 +443,27 @@ __global__ void k_gmat(const DevSys S, const double* __restrict__ g0, const doub
 }
 
 // ---------------------------------------------------------------------------------------------
+// phasor table of the real-drive frame of the lean column forward sweeps (qd_gauge.h: layout, and the arithmetic - gauge_osc,
+// gauge_row_phasor): one thread per (row of the control table, lane i < 64); the threads i < QD_MAX_OSC of a row also write r_i.
+// grid.y = parameter sets (launch_gauge_sets): set j reads table + j * ctl_set and writes gauge + j * gauge_set.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_gauge(const DevSys S, const double* __restrict__ table, int cs, int nrows, double* __restrict__ gauge, size_t ctl_set,
+                        size_t gauge_set) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (size_t)nrows * GAUGE_LANES) return;
+  const int row = (int)(e / GAUGE_LANES), i = (int)(e % GAUGE_LANES);
+  const double* r = table + (size_t)blockIdx.y * ctl_set + (size_t)row * cs;
+  double* out = gauge + (size_t)blockIdx.y * gauge_set + (size_t)row * GAUGE_STRIDE;
+  const double2 w = gauge_row_phasor(S, r, i);
+  out[2 * i] = w.x;
+  out[2 * i + 1] = w.y;
+  if (i < QD_MAX_OSC) {
+    double2 u;
+    out[GAUGE_R + i] = i < S.Q ? gauge_osc(r[2 + i], r[2 + S.Q + i], u) : 0.0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // ensemble mean of the gradient (qd_optim_evalGradF_ensemble): mean[i] (+)= sum_j w[j] g[j][i] over the nvar variants of one group,
 // one fma per variant in variant order; accumulate = 0 for the first group of a call (mean is overwritten), 1 for the others.
 // reg[nreg][ndesign]: the regularisation addends of the shared control vector, added to every variant's gradient one after the other
@@ -799,6 +821,24 @@ hipError_t launch_gmat_sets(const DevSys& S, const double* g0, size_t g0_set, co
   if (total == 0) return hipSuccess;
   hipLaunchKernelGGL(k_gmat, dim3((unsigned)((total + 255) / 256), nset), dim3(256), 0, st, S, g0, table, cs, nrows, gtab, ctl_set, gtab_set,
                      g0_set);
+  return hipGetLastError();
+}
+
+hipError_t launch_gauge(const DevSys& S, const double* table, int cs, int nrows, double* gauge, hipStream_t st) {
+  const size_t total = (size_t)nrows * GAUGE_LANES;
+  if (S.Q > QD_MAX_OSC || S.N > GAUGE_LANES) return hipErrorInvalidValue;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gauge, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, table, cs, nrows, gauge, (size_t)0, (size_t)0);
+  return hipGetLastError();
+}
+
+hipError_t launch_gauge_sets(const DevSys& S, const double* table, size_t ctl_set, int cs, int nrows, double* gauge, size_t gauge_set, int nset,
+                             hipStream_t st) {
+  const size_t total = (size_t)nrows * GAUGE_LANES;
+  if (S.Q > QD_MAX_OSC || S.N > GAUGE_LANES) return hipErrorInvalidValue;
+  if (nset < 1 || nset > 65535 || gauge_set < (size_t)nrows * GAUGE_STRIDE || ctl_set < (size_t)nrows * cs) return hipErrorInvalidValue;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gauge, dim3((unsigned)((total + 255) / 256), nset), dim3(256), 0, st, S, table, cs, nrows, gauge, ctl_set, gauge_set);
   return hipGetLastError();
 }
 

@@ -523,7 +523,8 @@ static double control_variation(const qd_handle* h, const double* alpha, double*
 }
 
 // gsets: the nb states are this many sets of a parameter-set batch on a dense user Hamiltonian - every set's table of G(t) lies in
-// memory beside the trajectory (qd_handle::batch_gtables) and is weighed with it (0: an ordinary evaluation, or the standard model)
+// memory beside the trajectory (qd_handle::batch_gtables) and is weighed with it (0: an ordinary evaluation, or the standard model) -
+// or on a lean column system, whose sets each have a phasor table there (qd_gauge.h; batch_gtab_set is the size of either)
 static bool trajectory_fits(qd_handle* h, int nb, const DevTarget* tg, int gsets = 0) {
   size_t need;
   h->traj_doubles(nb, &need);
@@ -1070,12 +1071,12 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
       int lo = gbytes > 0.0 ? (int)std::min((double)nset, std::floor(16e9 / gbytes)) : nset;  // lo sets fit, hi do not
       if (grad_mode && lo > 0) {  // the stored trajectory and stages of a group (and its G(t) tables): within what a single evaluation may allocate
         h->sets = 1;
-        const bool dense = h->S.dense != 0;
+        const bool tabs = h->batch_gtab_set() != 0;  // a table per set beside the trajectory: G(t) of a user Hamiltonian, the phasors of the lean column sweeps
         int hi = lo + 1;
-        lo = trajectory_fits(h, nl, &o->tg, dense ? 1 : 0) ? 1 : 0;
+        lo = trajectory_fits(h, nl, &o->tg, tabs ? 1 : 0) ? 1 : 0;
         while (lo > 0 && hi - lo > 1) {
           const int mid = lo + (hi - lo) / 2;
-          if (trajectory_fits(h, mid * nl, &o->tg, dense ? mid : 0)) lo = mid;
+          if (trajectory_fits(h, mid * nl, &o->tg, tabs ? mid : 0)) lo = mid;
           else hi = mid;
         }
       }
