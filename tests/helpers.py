@@ -62,18 +62,27 @@ def golden_rows(case, fname):
 
 def synthetic_cfg(nlevels, lindblad=True, ntime=20, dt=0.01, nspline=10, jkl=0.0, linsolve="neumann", stepper="IMR",
                   init="basis", target="gate", objective="Jtrace", nessential=None, maxiter=20, penalties=False,
-                  detuned=False, gate=None, segments=None, carrier="0.0, -0.2", ctrl_init="random, 0.005", enforce_bc=False):
-    """Synthetic systems in the style of SURVEY 8(d) / tests/performance/configs of the reference."""
+                  detuned=False, gate=None, segments=None, carrier="0.0, -0.2", ctrl_init="random, 0.005", enforce_bc=False,
+                  selfkerr=None, crosskerr=None, decay_time=None, dephase_time=None, jkl_pairs=None, collapse="both"):
+    """Synthetic systems in the style of SURVEY 8(d) / tests/performance/configs of the reference.
+
+    selfkerr, decay_time, dephase_time (one entry per oscillator), crosskerr, jkl_pairs (one entry per pair, in the order (0,1), (0,2), ...,
+    (1,2), ...; jkl_pairs replaces jkl) and collapse ("both" | "decay" | "dephase", Lindblad systems only) override the constants every
+    oscillator and pair shares by default (unequal_constants); without them the text is what it always was."""
     Q = len(nlevels)
+    assert collapse in ("both", "decay", "dephase"), collapse
+
+    def csv(values, default):
+        return default if values is None else ",".join(repr(float(v)) for v in values)
     lines = [
         "nlevels = " + ",".join(str(n) for n in nlevels),
         f"ntime = {ntime}", f"dt = {dt}",
         "transfreq = " + ",".join(f"{4.1 + 0.1 * k:.4f}" for k in range(Q)),
         "rotfreq = " + (",".join(["4.1"] * Q) if detuned else ",".join(f"{4.1 + 0.1 * k:.4f}" for k in range(Q))),
-        "selfkerr = " + ",".join(["0.2"] * Q),
-        "crosskerr = 0.001", f"Jkl = {jkl}",
-        "collapse_type = " + ("both" if lindblad else "none"),
-        "decay_time = " + ",".join(["80.0"] * Q), "dephase_time = " + ",".join(["26.0"] * Q),
+        "selfkerr = " + csv(selfkerr, ",".join(["0.2"] * Q)),
+        "crosskerr = " + csv(crosskerr, "0.001"), "Jkl = " + csv(jkl_pairs, f"{jkl}"),
+        "collapse_type = " + (collapse if lindblad else "none"),
+        "decay_time = " + csv(decay_time, ",".join(["80.0"] * Q)), "dephase_time = " + csv(dephase_time, ",".join(["26.0"] * Q)),
         f"initialcondition = {init}",
         "control_enforceBC = " + ("true" if enforce_bc else "false"),
         f"optim_objective = {objective}", "optim_regul = 1e-4",
@@ -103,6 +112,87 @@ def synthetic_cfg(nlevels, lindblad=True, ntime=20, dt=0.01, nspline=10, jkl=0.0
 
 def synthetic_spec(*args, **kw):
     return config.build_spec(config.parse_config_text(synthetic_cfg(*args, **kw)))
+
+
+def unequal_constants(Q, coupled=True, zero_pair=None):
+    """synthetic_cfg keywords that give every oscillator and every pair constants of its own, so that a kernel (or the host code that
+    fills its tables) reading them with the wrong oscillator or pair index computes something else: self-Kerr 0.2 + 0.07 k, T1 =
+    80 / (1 + 0.6 k), T2 = 26 / (1 + 0.45 k), cross-Kerr 0.05 (1 + 0.41 i), J = 0.02 (1 + 0.37 i) for oscillator k and pair i.  From
+    three oscillators on, oscillator 1 does not decay (decay_time = 0: no L1 term for it in a system that decays elsewhere).
+    coupled=False leaves J to the caller's jkl; zero_pair names one pair with J = 0 among the coupled ones."""
+    npairs = Q * (Q - 1) // 2
+    kw = dict(selfkerr=[0.2 + 0.07 * k for k in range(Q)],
+              decay_time=[0.0 if (k == 1 and Q >= 3) else 80.0 / (1.0 + 0.6 * k) for k in range(Q)],
+              dephase_time=[26.0 / (1.0 + 0.45 * k) for k in range(Q)],
+              crosskerr=[0.05 * (1.0 + 0.41 * i) for i in range(npairs)])
+    if coupled:
+        kw["jkl_pairs"] = [0.0 if i == zero_pair else 0.02 * (1.0 + 0.37 * i) for i in range(npairs)]
+    return kw
+
+
+def master_equation_rhs(sp, pq, t, x, transpose=False):
+    """The right-hand side of the rotating-frame master equation of spec `sp` at time t, applied to x = [Re; Im] (Lindblad: the
+    column-major vec of rho, src/util.cpp:150), from Kronecker products of ladder operators and nothing else (docs/mkdocs/user_guide.md,
+    model section):
+      H_d = sum_k (w_k - w_k^rot) n_k - xi_k/2 a^+a^+aa - sum_kl xi_kl n_k n_l
+            + sum_kl J_kl [cos(eta t)(a_k^+ a_l + a_k a_l^+) + i sin(eta t)(a_k^+ a_l - a_k a_l^+)],  eta = w_k^rot - w_l^rot
+      H_c = sum_k p_k (a_k + a_k^+) + i q_k (a_k - a_k^+),   L_1k = a_k / sqrt(T1_k),  L_2k = n_k / sqrt(T2_k)
+    with pq[k] = (p_k, q_k).  L_1k enters under collapse_type decay / both and L_2k under dephase / both, each only where its time is
+    above 1e-14 (src/mastereq.cpp:14-60).  transpose: the dense real matrix M of the operator, column by column from unit vectors, and
+    M^T x - for systems of a few hundred elements."""
+    from quandary_amd import capi
+    nl, sy = list(sp.nlevels), sp.system
+    Q, N, tw = len(nl), int(np.prod(nl)), 2 * np.pi
+    lindblad = sy.lindblad_type != capi.LINDBLAD["none"]
+    dim = N * N if lindblad else N
+    a = []
+    for k in range(Q):
+        op = np.array([[1.0 + 0j]])
+        for m in range(Q):
+            op = np.kron(op, np.diag(np.sqrt(np.arange(1, nl[m])), 1) if m == k else np.eye(nl[m]))
+        a.append(op)
+    dag = lambda m: m.conj().T
+    H = np.zeros((N, N), complex)
+    pair = 0
+    for k in range(Q):
+        nk = dag(a[k]) @ a[k]
+        H += tw * (sy.transfreq[k] - sy.rotfreq[k]) * nk - tw * sy.selfkerr[k] / 2 * (nk @ nk - nk)
+        for l in range(k + 1, Q):
+            eta, J = tw * (sy.rotfreq[k] - sy.rotfreq[l]), tw * sy.Jkl[pair]
+            H -= tw * sy.crosskerr[pair] * nk @ (dag(a[l]) @ a[l])
+            H += J * (np.cos(eta * t) * (dag(a[k]) @ a[l] + a[k] @ dag(a[l])) + 1j * np.sin(eta * t) * (dag(a[k]) @ a[l] - a[k] @ dag(a[l])))
+            pair += 1
+        H += pq[k][0] * (a[k] + dag(a[k])) + 1j * pq[k][1] * (a[k] - dag(a[k]))
+    collapse = []
+    if lindblad:
+        for k in range(Q):
+            if sy.lindblad_type in (capi.LINDBLAD["decay"], capi.LINDBLAD["both"]) and sy.decay_time[k] > 1e-14:
+                collapse.append(a[k] / np.sqrt(sy.decay_time[k]))
+            if sy.lindblad_type in (capi.LINDBLAD["dephase"], capi.LINDBLAD["both"]) and sy.dephase_time[k] > 1e-14:
+                collapse.append(dag(a[k]) @ a[k] / np.sqrt(sy.dephase_time[k]))
+    LdL = [dag(L) @ L for L in collapse]
+
+    def apply(v):
+        if not lindblad:
+            return -1j * (H @ (v[:dim] + 1j * v[dim:]))
+        rho = (v[:dim] + 1j * v[dim:]).reshape(N, N).T
+        y = -1j * (H @ rho - rho @ H)
+        for L, ll in zip(collapse, LdL):
+            y += L @ rho @ dag(L) - 0.5 * (ll @ rho + rho @ ll)
+        return y.T.reshape(-1)
+
+    x = np.asarray(x, dtype=float)
+    if not transpose:
+        return apply(x)
+    M = np.empty((2 * dim, 2 * dim))
+    e = np.zeros(2 * dim)
+    for j in range(2 * dim):
+        e[j] = 1.0
+        col = apply(e)
+        M[:dim, j], M[dim:, j] = col.real, col.imag
+        e[j] = 0.0
+    y = M.T @ x
+    return y[:dim] + 1j * y[dim:]
 
 
 # ---- parity of whole evaluations against the oracle -------------------------------------------------------------------------------------
