@@ -407,6 +407,35 @@ int qd_optim_evalGradF_ensemble(qd_optim* o, const double* alpha, int nvar, cons
                                 const double* weights, qd_objective_value* vals, qd_objective_value* mean, double* grads,
                                 double* grad_mean);
 
+/* The same for the STANDARD Hamiltonian model (a handle without qd_set_hamiltonian): ONE control vector on nvar variants of the model's
+ * constants - transition frequencies and self-Kerr coefficients [nvar][nosc], cross-Kerr coefficients and dipole-dipole couplings
+ * [nvar][npairs], GHz, in the pair order of qd_system.  Any of the four arrays may be NULL: the handle's own values for every variant.
+ * Variant j is the system of a handle created from the same qd_system with those arrays replaced (converted to rad/ns by the function
+ * qd_create uses); rotation frequencies - and with them the frame and the control table -, level counts, T1/T2, controls, target,
+ * penalties and initial conditions stay the handle's and the objective's.  vals, grads, mean, grad_mean, weights and
+ * qd_optim_last_batch_sets mean exactly what they mean for qd_optim_evalF_ensemble / qd_optim_evalGradF_ensemble (NULL weights = 1/nvar,
+ * vals and grads may be NULL, grad_mean by k_ensemble_mean).
+ * Errors: a user-Hamiltonian handle: QD_ERR_STATE (that handle uses the call above); an objective created with nranks > 1: QD_ERR_STATE;
+ * nvar < 1, a null alpha, mean or grad_mean, a non-finite constant, a negative or non-finite weight: QD_ERR_INVALID; a variant with
+ * |Jkl| > 1e-10 on a handle whose system has no coupling: QD_ERR_UNSUPPORTED (create the handle with a coupling; on a coupled handle a
+ * variant whose couplings are all zero is fine and stays on the coupled kernels, with zero weights).
+ * Shared launches: wherever the plan's sweep is a diagonal-split stationary iteration of the lean column family (Lindblad systems of two
+ * or three oscillators with 33..64 rows, the 3 x 20 class; a neumann request, or a gmres request served by the stand-in) all variants
+ * share one launch per sweep - k_forward_col_vars / k_adjoint_col_vars (coupled: k_*_colj_vars), each task reading its variant's
+ * constants from a device table; one plan for all variants from the largest row bounds among them; groups as in the batch.  Option
+ * batch_lean is not consulted; option ensemble_loop = 1 serves the call variant by variant instead (A/B switch).  Every other
+ * configuration - general, slot, fp32-mixed and global-memory families, plain-Neumann or Krylov column plans, chunked shards - goes
+ * variant by variant through the single evaluation with the handle pointed at one variant after the other: the numbers of a fresh
+ * handle, qd_optim_last_batch_sets = 1.
+ * After the call the state is that of a batch call; the handle's own constants, its solver latch and every table derived from them are
+ * what they were, and the next single evaluation returns what it returned before. */
+int qd_optim_evalF_ensemble_model(qd_optim* o, const double* alpha, int nvar, const double* transfreq, const double* selfkerr,
+                                  const double* crosskerr, const double* Jkl, const double* weights, qd_objective_value* vals,
+                                  qd_objective_value* mean);
+int qd_optim_evalGradF_ensemble_model(qd_optim* o, const double* alpha, int nvar, const double* transfreq, const double* selfkerr,
+                                      const double* crosskerr, const double* Jkl, const double* weights, qd_objective_value* vals,
+                                      qd_objective_value* mean, double* grads, double* grad_mean);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, initial conditions sharded over the ranks.
  * Replaces the reference's comm_init communicator (src/main.cpp:133-177) and its
@@ -466,7 +495,8 @@ int qd_set_precision(qd_handle* h, int precision);
  * Krylov kernels), gmres_poly (degree of the polynomial preconditioner, 0 = tuned then frozen, 1 = none), krylov_tau (double: the one-vector
  * path of the lean kernels' Krylov solvers accepts at residual <= krylov_tau x the reference's tolerance, default 0.1), krylov_restart (restart length of those solvers' generic path, 1 .. 14), force_neumann, var (kernel variant), no_mfma,
  * no_lean64, lean64_sb, no_collean, no_col_krylov, col_min_n, big_team, big_spread, big_blocked, traj_budget_mb (double), batch_lean (the parameter-set
- * batch shares launches on the lean slot, fp32-mixed and lean column families too: see qd_optim_evalF_batch; 0 = default).  Every key is also read from the
+ * batch shares launches on the lean slot, fp32-mixed and lean column families too: see qd_optim_evalF_batch; 0 = default), ensemble_loop (a model-parameter
+ * ensemble goes variant by variant even where it could share launches: see qd_optim_evalF_ensemble_model; 0 = default).  Every key is also read from the
  * environment variable QD_<KEY> once, at qd_create (tests, measurements).  Unknown keys: QD_ERR_INVALID. */
 int qd_set_option(qd_handle* h, const char* key, const char* value);
 int qd_get_precision(const qd_handle* h);

@@ -17,7 +17,13 @@ e22 / e16 / e27: the ensemble call (one control vector on nvar system Hamiltonia
 d22 / d16 / d27 against what it replaces - a loop of single evaluations over nvar handles, each prepared with its own Hsys before the
 clock starts; the variants are the workload's Hsys plus j x 0.1 % of a random Hermitian matrix of its size (64 samples span 6 %; a first run with 2 % per
 variant is recorded too: a launch lasts as long as its stiffest variant).
-usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 ...] > profiles/param_batch_probe.txt"""
+m320pure / m320diag / m320j: the model-parameter ensemble (evalGradF_ensemble_model / evalF_ensemble_model: one control vector on nvar
+variants of the standard model's constants) on the systems of c4pure / c4diag / c4jpure - the shared launches of k_*_col_vars against the
+same call under ensemble_loop = 1 (variant by variant on one handle) and against a loop of single evaluations over nvar handles, each
+created with its variant's constants before the clock starts.  Variant j: every transition frequency + j x 0.1 MHz, self- and cross-Kerr
+coefficients (and J_kl) x (1 + j x 1e-4).  The figure to hold it against is the parameter-set batch of the same set count (c4pure /
+c4diag / c4jpure): a variants launch should cost what that costs, plus the re-derivation per task.
+usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 m320pure m320diag m320j ...] > profiles/param_batch_probe.txt"""
 import os
 import sys
 import time
@@ -92,9 +98,75 @@ def ensemble_probe(which):
         h.close()
 
 
+MODEL = {"m320pure": "c4pure", "m320diag": "c4diag", "m320j": "c4jpure"}
+
+
+def model_variant(sp, j):
+    """The system block of variant j (a copy: the spec keeps its own)."""
+    s = type(sp.system).from_buffer_copy(sp.system)
+    Q = s.nosc
+    for k in range(Q):
+        s.transfreq[k] += 1e-4 * j
+        s.selfkerr[k] *= 1.0 + 1e-4 * j
+    for i in range(Q * (Q - 1) // 2):
+        s.crosskerr[i] *= 1.0 + 1e-4 * j
+        s.Jkl[i] *= 1.0 + 1e-4 * j
+    return s
+
+
+def model_probe(which):
+    workload, precision, options, nvars, overrides = PROBES[MODEL[which]]
+    for grad in (True, False):
+        def spec():
+            return workload_spec(workload, "gradient" if grad else "simulation", overrides)
+        sp = spec()
+        h, hl = capi.Handle(sp), capi.Handle(sp)
+        hl.set_option("ensemble_loop", "1")
+        o, ol = capi.Optim(h, sp), capi.Optim(hl, sp)
+        pairs = []
+        for j in range(max(nvars)):  # the comparator's handles: created with variant j's constants, outside the timed region
+            spj = spec()
+            spj.system = model_variant(sp, j)
+            hj = capi.Handle(spj)
+            pairs.append((hj, capi.Optim(hj, spj)))
+        alpha = sp.params0
+        for nvar in nvars:
+            variants = [model_variant(sp, j) for j in range(nvar)]
+            if grad:
+                forms = (("ensemble", lambda: o.evalGradF_ensemble_model(alpha, variants, per_variant=False)),
+                         ("loop", lambda: ol.evalGradF_ensemble_model(alpha, variants, per_variant=False)),
+                         ("single", lambda: [oj.evalGradF(alpha) for _, oj in pairs[:nvar]]))
+            else:
+                forms = (("ensemble", lambda: o.evalF_ensemble_model(alpha, variants)), ("loop", lambda: ol.evalF_ensemble_model(alpha, variants)),
+                         ("single", lambda: [oj.evalF(alpha) for _, oj in pairs[:nvar]]))
+            for _, fn in forms:
+                fn()  # (allocations, solver latch)
+            t = {tag: [] for tag, _ in forms}
+            for rep in range(2):
+                for tag, fn in forms:
+                    t0 = time.perf_counter()
+                    fn()
+                    t[tag].append((time.perf_counter() - t0) * 1e3)
+                    if tag == "ensemble":
+                        sets, kern = o.last_batch_sets, h.last_kernel("forward")
+            b, l, s = min(t["ensemble"]), min(t["loop"]), min(t["single"])
+            print(which, "grad" if grad else "fwd", "ninit", sp.ninit, "ntime", sp.time.ntime, "nvar", nvar, "variants_per_launch", sets,
+                  "ensemble_ms", " ".join("%.2f" % v for v in t["ensemble"]), "loop_ms", " ".join("%.2f" % v for v in t["loop"]),
+                  "single_ms", " ".join("%.2f" % v for v in t["single"]), "loop_over_ensemble %.2f" % (l / b),
+                  "single_over_ensemble %.2f" % (s / b), "ensemble_ms_per_variant %.3f" % (b / nvar), kern, flush=True)
+        for hj, oj in pairs:
+            oj.close()
+            hj.close()
+        for x in (o, ol, h, hl):
+            x.close()
+
+
 for which in (sys.argv[1:] or ["c1", "c3"]):
     if which in ENSEMBLE:
         ensemble_probe(which)
+        continue
+    if which in MODEL:
+        model_probe(which)
         continue
     workload, precision, options, nsets, overrides = PROBES[which]
     for grad in (True, False):

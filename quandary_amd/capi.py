@@ -181,6 +181,7 @@ EXPORTS = [
     "qd_comm_allreduce", "qd_comm_barrier", "qd_optim_evalF_dist", "qd_optim_evalGradF_dist", "qd_optim_last_chunks", "qd_set_precision", "qd_get_precision", "qd_bench_apply_f32", "qd_get_observables", "qd_set_option",
     "qd_optim_evalF_batch", "qd_optim_evalGradF_batch", "qd_optim_last_batch_sets",
     "qd_optim_evalF_ensemble", "qd_optim_evalGradF_ensemble",
+    "qd_optim_evalF_ensemble_model", "qd_optim_evalGradF_ensemble_model",
 ]
 COMM_ID_BYTES = 128
 PRECISION = {"f64": 0, "f32mixed": 1}
@@ -254,6 +255,10 @@ def load_library(path=None):
     lib.qd_optim_evalF_ensemble.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value), C.POINTER(qd_objective_value)]
     lib.qd_optim_evalGradF_ensemble.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value),
                                                 C.POINTER(qd_objective_value), c_dp, c_dp]
+    lib.qd_optim_evalF_ensemble_model.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value),
+                                                  C.POINTER(qd_objective_value)]
+    lib.qd_optim_evalGradF_ensemble_model.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value),
+                                                      C.POINTER(qd_objective_value), c_dp, c_dp]
     lib.qd_comm_unique_id.argtypes = [c_u8p]
     lib.qd_comm_create.argtypes = [c_u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.qd_comm_create_from_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp)]
@@ -618,6 +623,52 @@ class Optim:
         gm = np.zeros(max(nd, 1))
         _check(self.lib, self.lib.qd_optim_evalGradF_ensemble(self._o, dptr(alpha), nvar, dptr(sr), dptr(si), dptr(w), vals, C.byref(mean),
                                                               dptr(g), dptr(gm)), "qd_optim_evalGradF_ensemble")
+        return (mean.as_dict(), gm[:nd], [vals[j].as_dict() for j in range(nvar)],
+                np.ascontiguousarray(g[:nvar, :nd]) if per_variant else None)
+
+    # one control vector on several variants of the standard model's constants: variants = objects with transfreq / selfkerr /
+    # crosskerr / Jkl attributes in GHz (a spec's .system), of which the first nosc / npairs entries are read
+    def _ensemble_model_args(self, alpha, variants, weights):
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        nvar = len(variants)
+        nosc = self.h.spec.system.nosc
+        npairs = nosc * (nosc - 1) // 2
+
+        def rows(name, n):
+            a = np.zeros((max(nvar, 1), max(n, 1)))
+            for j, v in enumerate(variants):
+                a[j, :n] = np.asarray(getattr(v, name), dtype=np.float64).ravel()[:n]
+            return a
+
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(nvar)
+        return alpha, nvar, rows("transfreq", nosc), rows("selfkerr", nosc), rows("crosskerr", npairs), rows("Jkl", npairs), w
+
+    def evalF_ensemble_model(self, alpha, variants, weights=None):
+        """qd_optim_evalF_ensemble_model: (mean dict, list of dicts).  Variant j is this handle's system (standard model, no
+        set_hamiltonian) with transfreq / selfkerr / crosskerr / Jkl replaced by variants[j]'s, evaluated as evalF(alpha) on a handle
+        created from that system; every field of the mean is sum_j weights[j] x that field (weights as given, None = 1 / nvar each).
+        The variants share sweep launches where the plan is a diagonal-split stationary iteration of the lean column kernels
+        (last_batch_sets; option ensemble_loop = 1: variant by variant), everything else goes variant by variant."""
+        alpha, nvar, tf, sk, ck, jk, w = self._ensemble_model_args(alpha, variants, weights)
+        vals = (qd_objective_value * max(nvar, 1))()
+        mean = qd_objective_value()
+        _check(self.lib, self.lib.qd_optim_evalF_ensemble_model(self._o, dptr(alpha), nvar, dptr(tf), dptr(sk), dptr(ck), dptr(jk), dptr(w),
+                                                                vals, C.byref(mean)), "qd_optim_evalF_ensemble_model")
+        return mean.as_dict(), [vals[j].as_dict() for j in range(nvar)]
+
+    def evalGradF_ensemble_model(self, alpha, variants, weights=None, per_variant=True):
+        """qd_optim_evalGradF_ensemble_model: (mean dict, grad_mean [ndesign], list of dicts, gradients [nvar, ndesign] or None).
+        grad_mean = sum_j weights[j] x gradient of variant j (k_ensemble_mean where the variants share launches); per_variant = False
+        leaves the single gradients on the device (grads = None)."""
+        alpha, nvar, tf, sk, ck, jk, w = self._ensemble_model_args(alpha, variants, weights)
+        vals = (qd_objective_value * max(nvar, 1))()
+        mean = qd_objective_value()
+        nd = self.h.ndesign
+        g = np.zeros((max(nvar, 1), max(nd, 1))) if per_variant else None
+        gm = np.zeros(max(nd, 1))
+        _check(self.lib, self.lib.qd_optim_evalGradF_ensemble_model(self._o, dptr(alpha), nvar, dptr(tf), dptr(sk), dptr(ck), dptr(jk),
+                                                                    dptr(w), vals, C.byref(mean), dptr(g), dptr(gm)),
+               "qd_optim_evalGradF_ensemble_model")
         return (mean.as_dict(), gm[:nd], [vals[j].as_dict() for j in range(nvar)],
                 np.ascontiguousarray(g[:nvar, :nd]) if per_variant else None)
 

@@ -28,7 +28,19 @@
 #ifndef QD_COL_SETS
 #define QD_COL_SETS 0
 #endif
-#if QD_COL_SETS
+// With QD_COL_VARS 1 (set by qd_col_vars.hip / qd_colj_vars.hip, objects of their own): the third form, k_*_col_vars / k_*_colj_vars - one
+// block of model constants per variant (model-parameter ensemble, qd_optim_evalGradF_ensemble_model).  The task of initial condition ic
+// belongs to variant ic / SweepArgs::nb_set: it reads that variant's control and phasor tables as the SETS form does, and its detunings,
+// Kerr coefficients and couplings from the device table of qd_col_vars.h through the scalar path.  Everything ColLean::init derives from
+// those constants is derived again, by the same text, when a workgroup's task belongs to another variant than its previous one
+// (col_vars_enter below).  Only the diagonal-split stationary instantiations are built.
+#ifndef QD_COL_VARS
+#define QD_COL_VARS 0
+#endif
+#if QD_COL_VARS
+#include "qd_col_vars.h"
+#endif
+#if QD_COL_SETS || QD_COL_VARS
 #define QD_COL_CTL(A, ic) (A.ctl + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * A.ctl_set)
 #define QD_COL_GAUGE_TAB(A, ic) (gauge_tab(A) + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * gauge_set(A))
 #else
@@ -72,6 +84,15 @@ enum : int { KET_NONE = 0, KET_BOTTOM = 1, KET_INTERIOR = 2, KET_TOP = 3 };
 #ifndef QD_COL_GAUGE_AHEAD
 #define QD_COL_GAUGE_AHEAD 0
 #endif
+
+// The model constants ColLean::init derives a kernel's values from, read from the kernel argument (every form but QD_COL_VARS)
+struct ColSysConsts {
+  const DevSys& S;
+  __device__ __forceinline__ double detune(int k) const { return S.detune[k]; }
+  __device__ __forceinline__ double xi(int k) const { return S.xi[k]; }
+  __device__ __forceinline__ double xikl(int p) const { return S.xikl[p]; }
+  __device__ __forceinline__ double J(int p) const { return S.J[p]; }
+};
 
 // SPLIT: the kernels of the diagonal-split solver keep (1 - alpha D)^-1 per element instead of the diagonal itself; the diagonal is then
 // re-derived where the full operator is applied (once or twice per step) from a row part held by the thread and a column part in LDS
@@ -136,37 +157,47 @@ struct ColLean {
 
   // PERM (USLOT): wave w takes the column block EPT (w / n_0) of level w % n_0 of oscillator 0 - consecutive waves, which share a SIMD
   // every fourth, are of different ket classes
-  template <bool PERM = false>
-  __device__ __forceinline__ void init(const DevSys& S, unsigned char* sm) {
-    smem = sm;
-    N = S.N;
+  // K: where the model constants (detuning, self- and cross-Kerr coefficients, couplings) are read - the kernel argument (ColSysConsts),
+  // or one variant's block of the constants table (ColVarConsts of qd_col_vars.h, the third form).
+  // FIRST = false: only what depends on those constants is derived again, for another variant - hrow, the column table, dw, the
+  // coupling weights sj1 / sj2 / kj3 / kj4 and the address offsets aj1 / aj2 / oj3 / oj4 a non-zero weight selects - by THIS text: every
+  // element gets the bits the plain kernel computes.  The caller holds the workgroup at a barrier before (the column table is rewritten)
+  // and after, and resets ColTeam::palpha.
+  template <bool PERM = false, bool FIRST = true, class KC = ColSysConsts>
+  __device__ __forceinline__ void init(const DevSys& S, unsigned char* sm, const KC& K) {
     const int lane = threadIdx.x & 63;
-    const int w = uniform_i((int)(threadIdx.x >> 6));
-    col0 = w * EPT;
-    if constexpr (PERM) {
-      const int n0 = S.n[0];
-      if ((int)(blockDim.x >> 6) % n0 == 0) col0 = uniform_i(S.post[0] * (w % n0) + EPT * (w / n0));
+    if constexpr (FIRST) {
+      smem = sm;
+      N = S.N;
+      const int w = uniform_i((int)(threadIdx.x >> 6));
+      col0 = w * EPT;
+      if constexpr (PERM) {
+        const int n0 = S.n[0];
+        if ((int)(blockDim.x >> 6) % n0 == 0) col0 = uniform_i(S.post[0] * (w % n0) + EPT * (w / n0));
+      }
+      row = lane;
+      rowok = lane < N;
+      // zero the exchange buffers once: padding rows and idle columns are read (with zero coefficients) and must stay finite
+      {
+        const unsigned total = 2 * bufbytes(N);
+        for (unsigned a = threadIdx.x * 16u; a < total; a += blockDim.x * 16u) st(a, make_double2(0.0, 0.0));
+      }
+      tb = (unsigned)col0 * COLB + (unsigned)lane * 16u;
+      dlt = (int)bufbytes(N);
     }
-    row = lane;
-    rowok = lane < N;
-    // zero the exchange buffers once: padding rows and idle columns are read (with zero coefficients) and must stay finite
-    {
-      const unsigned total = 2 * bufbytes(N);
-      for (unsigned a = threadIdx.x * 16u; a < total; a += blockDim.x * 16u) st(a, make_double2(0.0, 0.0));
-    }
-    tb = (unsigned)col0 * COLB + (unsigned)lane * 16u;
-    dlt = (int)bufbytes(N);
     int ia[Q];
     double hd = 0.0;  // h(I)
 #pragma unroll
     for (int k = 0; k < Q; k++) {
       ia[k] = rowok ? (row / S.post[k]) % S.n[k] : 0;
-      su[k] = (rowok && ia[k] < S.n[k] - 1) ? sqrt((double)(ia[k] + 1)) : 0.0;
-      sd[k] = rowok ? sqrt((double)ia[k]) : 0.0;
-      g1u[k] = S.g1off[k] * su[k];
-      g1d[k] = S.g1off[k] * sd[k];
-      aru[k] = tb + (su[k] != 0.0 ? (unsigned)S.post[k] * 16u : 0u);
-      ard[k] = tb - (sd[k] != 0.0 ? (unsigned)S.post[k] * 16u : 0u);
+      if constexpr (FIRST) {
+        su[k] = (rowok && ia[k] < S.n[k] - 1) ? sqrt((double)(ia[k] + 1)) : 0.0;
+        sd[k] = rowok ? sqrt((double)ia[k]) : 0.0;
+        g1u[k] = S.g1off[k] * su[k];
+        g1d[k] = S.g1off[k] * sd[k];
+        aru[k] = tb + (su[k] != 0.0 ? (unsigned)S.post[k] * 16u : 0u);
+        ard[k] = tb - (sd[k] != 0.0 ? (unsigned)S.post[k] * 16u : 0u);
+      }
     }
     if constexpr (HJ) {
       int pair = 0;
@@ -175,8 +206,8 @@ struct ColLean {
 #pragma unroll
         for (int l = k + 1; l < Q; l++, pair++) {
           // (a non-zero weight means 0 < i_k and i_l < n_l - 1, resp. 0 < i_l and i_k < n_k - 1: the neighbour row is inside the column)
-          sj1[pair] = S.J[pair] * sd[k] * su[l];
-          sj2[pair] = S.J[pair] * sd[l] * su[k];
+          sj1[pair] = K.J(pair) * sd[k] * su[l];
+          sj2[pair] = K.J(pair) * sd[l] * su[k];
           const unsigned d = (unsigned)(S.post[l] - S.post[k]) * 16u;
           aj1[pair] = tb + (sj1[pair] != 0.0 ? d : 0u);
           aj2[pair] = tb - (sj2[pair] != 0.0 ? d : 0u);
@@ -187,20 +218,22 @@ struct ColLean {
       int pair = 0;
 #pragma unroll
       for (int k = 0; k < Q; k++) {
-        hd += S.detune[k] * ia[k] - S.xi[k] / 2.0 * ia[k] * (ia[k] - 1);
+        hd += K.detune(k) * ia[k] - K.xi(k) / 2.0 * ia[k] * (ia[k] - 1);
 #pragma unroll
-        for (int l = k + 1; l < Q; l++) hd -= S.xikl[pair++] * ia[k] * ia[l];
+        for (int l = k + 1; l < Q; l++) hd -= K.xikl(pair++) * ia[k] * ia[l];
       }
     }
     hrow = rowok ? hd : 0.0;
-    drow = 0.0;
+    if constexpr (FIRST) {
+      drow = 0.0;
 #pragma unroll
-    for (int k = 0; k < Q; k++) {
-      drow -= 0.5 * S.g2[k] * ia[k] * ia[k] + 0.5 * S.g1[k] * ia[k];
-      g2ia[k] = rowok ? S.g2[k] * ia[k] : 0.0;
+      for (int k = 0; k < Q; k++) {
+        drow -= 0.5 * S.g2[k] * ia[k] * ia[k] + 0.5 * S.g1[k] * ia[k];
+        g2ia[k] = rowok ? S.g2[k] * ia[k] : 0.0;
+      }
+      if (!rowok) drow = 0.0;
+      ctb = tab_off(N) + (unsigned)col0 * 48u;
     }
-    if (!rowok) drow = 0.0;
-    ctb = tab_off(N) + (unsigned)col0 * 48u;
     if (SPLIT) {  // column table: (h(I'), column part of d), (i'_0, i'_1), (i'_2, 0); zeros for idle columns
       for (int cc = threadIdx.x; cc < ncols(N); cc += blockDim.x) {
         double hc = 0.0, dc = 0.0, ip[3] = {0.0, 0.0, 0.0};
@@ -210,11 +243,11 @@ struct ColLean {
           for (int k = 0; k < Q; k++) ipa[k] = (cc / S.post[k]) % S.n[k];
 #pragma unroll
           for (int k = 0; k < Q; k++) {
-            hc += S.detune[k] * ipa[k] - S.xi[k] / 2.0 * ipa[k] * (ipa[k] - 1);
+            hc += K.detune(k) * ipa[k] - K.xi(k) / 2.0 * ipa[k] * (ipa[k] - 1);
             dc -= 0.5 * S.g2[k] * ipa[k] * ipa[k] + 0.5 * S.g1[k] * ipa[k];
             ip[k] = (double)ipa[k];
 #pragma unroll
-            for (int l = k + 1; l < Q; l++) hc -= S.xikl[pair++] * ipa[k] * ipa[l];
+            for (int l = k + 1; l < Q; l++) hc -= K.xikl(pair++) * ipa[k] * ipa[l];
           }
         }
         double2* t = reinterpret_cast<double2*>(smem + tab_off(N) + (unsigned)cc * 48u);
@@ -234,18 +267,20 @@ struct ColLean {
       for (int k = 0; k < Q; k++) ipa[k] = cok ? (cc / S.post[k]) % S.n[k] : 0;
 #pragma unroll
       for (int k = 0; k < Q; k++) {
-        hdp += S.detune[k] * ipa[k] - S.xi[k] / 2.0 * ipa[k] * (ipa[k] - 1);
+        hdp += K.detune(k) * ipa[k] - K.xi(k) / 2.0 * ipa[k] * (ipa[k] - 1);
         d += S.g2[k] * (ia[k] * ipa[k] - 0.5 * (ia[k] * ia[k] + ipa[k] * ipa[k])) - S.g1[k] / 2.0 * (ia[k] + ipa[k]);
 #pragma unroll
-        for (int l = k + 1; l < Q; l++) hdp -= S.xikl[pair++] * ipa[k] * ipa[l];
-        const bool up = cok && ipa[k] < S.n[k] - 1, dn = cok && ipa[k] > 0;
-        cx[j][k] = to_scalar(up ? sqrt((double)(ipa[k] + 1)) : 0.0);
-        cy[j][k] = to_scalar(dn ? sqrt((double)ipa[k]) : 0.0);
-        if (!USLOT || j == 0 || k == L) {
-          // (USLOT: the offsets of the stride-1 oscillator are only used at the two edge slots, whose neighbours are not in registers:
-          //  the up offset of the last slot, the down offset of the first)
-          if (!USLOT || k != L || j == 0) ocd[us(j)][k] = uniform_i(dn ? -S.post[k] * (int)COLB : 0);
-          if (!USLOT || k != L || j == EPT - 1 || EPT == 1) ocu[us(j)][k] = uniform_i(up ? S.post[k] * (int)COLB : 0);
+        for (int l = k + 1; l < Q; l++) hdp -= K.xikl(pair++) * ipa[k] * ipa[l];
+        if constexpr (FIRST) {
+          const bool up = cok && ipa[k] < S.n[k] - 1, dn = cok && ipa[k] > 0;
+          cx[j][k] = to_scalar(up ? sqrt((double)(ipa[k] + 1)) : 0.0);
+          cy[j][k] = to_scalar(dn ? sqrt((double)ipa[k]) : 0.0);
+          if (!USLOT || j == 0 || k == L) {
+            // (USLOT: the offsets of the stride-1 oscillator are only used at the two edge slots, whose neighbours are not in registers:
+            //  the up offset of the last slot, the down offset of the first)
+            if (!USLOT || k != L || j == 0) ocd[us(j)][k] = uniform_i(dn ? -S.post[k] * (int)COLB : 0);
+            if (!USLOT || k != L || j == EPT - 1 || EPT == 1) ocu[us(j)][k] = uniform_i(up ? S.post[k] * (int)COLB : 0);
+          }
         }
       }
       if constexpr (HJ) {
@@ -255,7 +290,7 @@ struct ColLean {
 #pragma unroll
           for (int l = k + 1; l < Q; l++, pj++) {
             if (uj(j, pj) != j) continue;
-            const double w3 = S.J[pj] * cy[j][k] * cx[j][l], w4 = S.J[pj] * cy[j][l] * cx[j][k];
+            const double w3 = K.J(pj) * cy[j][k] * cx[j][l], w4 = K.J(pj) * cy[j][l] * cx[j][k];
             kj3[j][pj] = to_scalar(w3);
             kj4[j][pj] = to_scalar(w4);
             oj3[j][pj] = uniform_i(w3 != 0.0 ? (S.post[l] - S.post[k]) * (int)COLB : 0);
@@ -266,9 +301,13 @@ struct ColLean {
       const bool live = rowok && cok;
       if (!SPLIT) {
         dw[j] = live ? hd - hdp : 0.0;
-        dd[j] = live ? d : 0.0;
+        if (FIRST) dd[j] = live ? d : 0.0;
       }
     }
+  }
+  template <bool PERM = false>
+  __device__ __forceinline__ void init(const DevSys& S, unsigned char* sm) {
+    init<PERM, true>(S, sm, ColSysConsts{S});
   }
 
   // diagonal of M at the element in slot j: (Delta, d)
@@ -500,6 +539,22 @@ struct ColTeam {
     if (threadIdx.x < 32) reinterpret_cast<float*>(fred)[threadIdx.x] = 0.f;  // (16 partial sums are read whatever the number of waves)
     __syncthreads();  // zero fill complete
   }
+
+#if QD_COL_VARS
+  // The task about to run belongs to variant ic / nb_set: where that is not the variant of the workgroup's previous task (*cur; -1 before
+  // the first), everything init derived from the model constants is derived again from the variant's block (ColLean::init<.., false>).
+  // Workgroup-uniform; the barriers fence the column table, which every wave reads.  palpha = 0: the next set_alpha forms
+  // (1 - alpha D)^-1 anew - and, FOLD, the T1 factors, which do not depend on the variant, to the same bits.
+  __device__ __forceinline__ void enter_variant(const SweepArgs& A, int ic, int* cur) {
+    const int var = uniform_i((int)((unsigned)ic / (unsigned)A.nb_set));
+    if (var == *cur) return;
+    *cur = var;
+    __syncthreads();
+    st.template init<false, false>(A.S, st.smem, ColVarConsts<Q>{col_vars_tab(A) + (size_t)var * col_vars_stride(Q, ST::NP)});
+    palpha = 0.0;
+    __syncthreads();
+  }
+#endif
 
   // x becomes the vector being read
   __device__ __forceinline__ void publish(const double2 (&x)[EPT]) {
@@ -1335,12 +1390,18 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   tm.init(S, smem);
   if constexpr (KRY) tm.init_kry(A);
   __shared__ unsigned task_slot, carry_slot;
+#if QD_COL_VARS
+  int curvar = -1;  // variant of the workgroup's previous task (ColTeam::enter_variant)
+#endif
   const int dim = S.dim, ntask = A.nb * A.nslice;
   const bool pen_on = A.gamma_penalty > 1e-13;
   const bool wj_on = pen_on && A.penalty_param > 1e-13;
   const bool leak = pen_on && A.leak_on && tm.st.row_is_guard(S);
   for (int task = A.sched ? sched_next(A.sched, &task_slot) : (int)blockIdx.x; task < ntask; task = A.sched ? sched_next(A.sched, &task_slot) : ntask) {
   const int ic = task % A.nb, sl = task / A.nb;
+#if QD_COL_VARS
+  tm.enter_variant(A, ic, &curvar);
+#endif
   const int s_lo = slice_start(A, sl), s_hi = slice_start(A, sl + 1);
   tm.lastn = 0;  // (the pass count of the previous sub-step: none at t = 0, otherwise what the previous slice hands over)
   if (sl > 0 && !sched_wait(A.sched, ic, (unsigned)sl, A.sched_ticks, &carry_slot, &tm.lastn)) return;
@@ -1352,6 +1413,19 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
     for (int j = 0; j < EPT; j++) x[j] = tm.st.ok(j) ? make_double2(x0[tm.st.elem(j)], x0[dim + tm.st.elem(j)]) : make_double2(0.0, 0.0);
   }
   double pen_local = 0.0, pen_uniform = 0.0;
+#if QD_COL_VARS
+  // A time-sliced sweep of this form carries every thread's penalty sum from slice to slice (qd_col_vars.h: one block of
+  // COL_VARS_PEN_STRIDE doubles per state, the uniform part in its last word) and reduces it once, behind the last slice: the additions
+  // of a thread are those of the unsliced sweep in the same order, so a sliced call returns the bits of an unsliced one - penalties
+  // included.  The predecessor's stores are visible like its state in A.xT (sched_done / sched_wait).
+  // (the block's address is formed where it is used, from kernel arguments: nothing of it lives across the time loop)
+  if (A.sched && sl > 0) {
+    const double* pc = col_vars_pen_carry(A) + (size_t)ic * COL_VARS_PEN_STRIDE;
+    pen_local = pc[threadIdx.x];
+    // (the uniform part exists where the rotated-frame form does not fold it into the thread sums; wave-uniform: scalar registers)
+    if constexpr (!TM::GAUGE) pen_uniform = to_scalar(pc[COL_VARS_PEN_STRIDE - 1]);
+  }
+#endif
   unsigned long long napply = 0;
   // global accesses of the thread's elements: one divergent region per call (rows), uniform branches inside (columns)
   auto store_state = [&](double* dst, const double2(&v)[EPT], bool nt) {
@@ -1455,6 +1529,22 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   }
   store_state(A.xT + (size_t)ic * 2 * dim, x, false);
   if (A.traj && sl == A.nslice - 1) store_state(A.traj + ((size_t)A.nsub * A.nb + ic) * 2 * dim, x, false);
+#if QD_COL_VARS
+  if (A.sched && sl < A.nslice - 1) {  // not the last slice: the thread's sum travels on
+    double* pcarry = col_vars_pen_carry(A) + (size_t)ic * COL_VARS_PEN_STRIDE;
+    pcarry[threadIdx.x] = pen_local;
+    if constexpr (!TM::GAUGE)
+      if (threadIdx.x == 0) pcarry[COL_VARS_PEN_STRIDE - 1] = pen_uniform;
+  }
+  // (one path for every slice: the reduction of a slice that is not the last is not used - the last one's is the sweep's)
+  double v[1] = {pen_local};
+  tm.template sum<1>(v);
+  if (threadIdx.x == 0) {
+    A.pen_out[ic] = 0.0 + v[0] + pen_uniform;  // (the expression of the other forms at sl = 0)
+    A.dpdm_out[ic] = 0.0;
+    atomicAdd(A.napply, napply);
+  }
+#else
   double v[1] = {pen_local};
   tm.template sum<1>(v);
   if (threadIdx.x == 0) {
@@ -1462,6 +1552,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
     A.dpdm_out[ic] = 0.0;  // the dpdm penalty is Schroedinger only (timestepper.cpp:143-146)
     atomicAdd(A.napply, napply);
   }
+#endif
   if (A.sched) sched_done(A.sched, ic, (unsigned)(sl + 1), tm.lastn);
   }
 }
@@ -1480,6 +1571,9 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
   tm.init(S, smem);
   if constexpr (KRY) tm.init_kry(A);
   __shared__ unsigned task_slot, carry_slot;
+#if QD_COL_VARS
+  int curvar = -1;  // variant of the workgroup's previous task (ColTeam::enter_variant)
+#endif
   const int dim = S.dim, ntask = A.nb * A.nslice;
   const bool pen_on = A.gamma_penalty > 1e-13;
   const bool wj_on = pen_on && A.penalty_param > 1e-13;
@@ -1487,6 +1581,9 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
   for (int task = A.sched ? sched_next(A.sched, &task_slot) : (int)blockIdx.x; task < ntask; task = A.sched ? sched_next(A.sched, &task_slot) : ntask) {
   // backwards in time: task slice sl covers the time slice nslice - 1 - sl
   const int ic = task % A.nb, sl = task / A.nb;
+#if QD_COL_VARS
+  tm.enter_variant(A, ic, &curvar);
+#endif
   const int s_lo = slice_start(A, A.nslice - 1 - sl), s_hi = slice_start(A, A.nslice - sl);
   tm.lastna = 0;
   if (sl > 0 && !sched_wait(A.sched, ic, (unsigned)sl, A.sched_ticks, &carry_slot, &tm.lastna)) return;
@@ -1708,6 +1805,17 @@ static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
+#if QD_COL_VARS
+  // the third form is built for the diagonal-split stationary iteration only (a plain-Neumann or Krylov plan goes variant by variant,
+  // qd_optim.cpp): anything else is an error, and nothing of it is instantiated
+  if (a.use_gmres || !a.neumann_split) return hipErrorInvalidValue;
+  if constexpr (QD_COL_HJ) {
+    return go(yes, no, no);
+  } else {
+    const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;  // (the rule of the other forms)
+    return skip ? go(yes, yes, no) : go(yes, no, no);
+  }
+#else
   if constexpr (QD_COL_SETS) {  // (no SETS form of the Krylov kernels: an error, and nothing instantiated)
     if (a.use_gmres) return hipErrorInvalidValue;
   } else {
@@ -1723,6 +1831,7 @@ static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
     if (a.neumann_split) return skip ? go(yes, yes, no) : go(yes, no, no);
     return skip ? go(no, yes, no) : go(no, no, no);
   }
+#endif
 }
 
 // One operator application.  SPLIT selects the kernel family that re-derives the diagonal from its compact form (uncoupled: the option
@@ -1752,9 +1861,10 @@ static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const
     return hipErrorInvalidValue;                                                       \
   } while (0)
 
-#if QD_COL_SETS
-// The SETS units: a.nb states = a.nb / a.nb_set sets, each reading its own control table.  A request they cannot serve - the Krylov
-// solver, states that do not divide into sets - is an error, never another kernel.
+#if QD_COL_SETS || QD_COL_VARS
+// The SETS units (and the units of the third form, QD_COL_VARS: a set is a variant): a.nb states = a.nb / a.nb_set sets, each reading its
+// own control table.  A request they cannot serve - the Krylov solver, states that do not divide into sets - is an error, never another
+// kernel.
 static bool col_sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
 // One object per <Q, EPT> (QD_COL_SETS_Q, QD_COL_SETS_EPT on the command line: they compile side by side) holds that case's col_sweep and
 // with it its kernels; the object built without the two holds the unit's entry point, which reaches them through QD_COL_DISPATCH.

@@ -71,7 +71,7 @@ extern "C" void qd_destroy(qd_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
-  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0}) b->release();
+  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0, &h->d_vconst, &h->d_pencarry}) b->release();
   h->h_bparams.release();
   h->h_betable.release();
   h->h_bgrad.release();
@@ -152,8 +152,9 @@ extern "C" int qd_create(const qd_system* sys, const qd_controls* ctl, const qd_
   for (int k = 0; k < S.Q; k++) {
     S.post[k] = 1;
     for (int j = k + 1; j < S.Q; j++) S.post[k] *= S.n[j];
-    S.detune[k] = 2.0 * M_PI * (sys->transfreq[k] - sys->rotfreq[k]);
-    S.xi[k] = 2.0 * M_PI * sys->selfkerr[k];
+    S.detune[k] = model_detune(sys->transfreq[k], sys->rotfreq[k]);
+    S.xi[k] = model_kerr(sys->selfkerr[k]);
+    h->rotfreq.push_back(sys->rotfreq[k]);
     S.g1[k] = (sys->decay_time[k] > 1e-14 && addT1) ? 1.0 / sys->decay_time[k] : 0.0;
     S.g1off[k] = fabs(S.g1[k]) > 1e-12 ? S.g1[k] : 0.0;  // threshold of L1decay (mastereq.hpp:759)
     S.g2[k] = (sys->dephase_time[k] > 1e-14 && addT2) ? 1.0 / sys->dephase_time[k] : 0.0;
@@ -164,10 +165,9 @@ extern "C" int qd_create(const qd_system* sys, const qd_controls* ctl, const qd_
   int idx = 0;
   for (int k = 0; k < S.Q; k++)
     for (int l = k + 1; l < S.Q; l++) {
-      S.xikl[idx] = 2.0 * M_PI * sys->crosskerr[idx];
-      S.J[idx] = 2.0 * M_PI * sys->Jkl[idx];
-      if (!(fabs(S.J[idx]) > 1e-10)) S.J[idx] = 0.0;  // threshold of Jkl_coupling (mastereq.hpp:633)
-      else S.hasJ = 1;
+      S.xikl[idx] = model_kerr(sys->crosskerr[idx]);
+      S.J[idx] = model_coupling(sys->Jkl[idx]);
+      if (S.J[idx] != 0.0) S.hasJ = 1;
       D.eta[idx] = 2.0 * M_PI * (sys->rotfreq[k] - sys->rotfreq[l]);
       idx++;
     }
@@ -546,6 +546,10 @@ int qd_handle::batch_begin(const double* alphas, int nset) {
     batch_bound.off = std::max(batch_bound.off, of);
   }
   params = keep;
+  if (vars_tab) {  // a model-parameter ensemble: the bounds of its variants (variants_upload), not of the handle's own constants
+    batch_bound.diag = vars_bound.diag;
+    batch_bound.off = vars_bound.off;
+  }
   for (double hh : sched_h) batch_bound.amax = std::max(batch_bound.amax, fabs(hh) / 2.0);
   params_set = true;  // (the gates have controls to look at)
   traj_valid = false;
@@ -597,6 +601,84 @@ int qd_handle::ensemble_upload(int nvar, const double* hsys_re, const double* hs
   int r;
   if ((r = d_eg0.ensure(g0.size()))) return r;
   QD_HIP(hipMemcpy(d_eg0.p, g0.data(), sizeof(double) * g0.size(), hipMemcpyHostToDevice));
+  return QD_OK;
+}
+
+// Model-parameter ensemble: the model constants of the handle as they stand, and their replacement.  Derived from them at qd_create or
+// on first use, and therefore swapped with them: the cached bound of the level energies (row_bounds) and the per-element table of the
+// global-memory kernels (ensure_big builds it again before the next sweep that reads it).  hasJ stays: a handle keeps its kernels.
+qd_handle::ModelConstants qd_handle::model_constants_now() const {
+  ModelConstants m{};
+  for (int k = 0; k < S.Q; k++) {
+    m.detune[k] = S.detune[k];
+    m.xi[k] = S.xi[k];
+  }
+  for (int p = 0; p < S.npairs; p++) {
+    m.xikl[p] = S.xikl[p];
+    m.J[p] = S.J[p];
+  }
+  m.hmax = hmax_cache;
+  return m;
+}
+
+void qd_handle::set_model_constants(const ModelConstants& m) {
+  for (int k = 0; k < S.Q; k++) {
+    S.detune[k] = m.detune[k];
+    S.xi[k] = m.xi[k];
+  }
+  for (int p = 0; p < S.npairs; p++) {
+    S.xikl[p] = m.xikl[p];
+    S.J[p] = m.J[p];
+  }
+  hmax_cache = m.hmax;
+  ecoef_valid = false;
+  traj_valid = false;
+}
+
+// the handle as qd_create would have made it with variant j's constants: the stand-in gates undecided, no table of another system
+void qd_handle::point_at_variant(int j) {
+  const double* b = vars_host.data() + (size_t)j * col_vars_stride(S.Q, S.npairs);
+  ModelConstants m{};
+  for (int k = 0; k < S.Q; k++) {
+    m.detune[k] = b[k];
+    m.xi[k] = b[S.Q + k];
+  }
+  for (int p = 0; p < S.npairs; p++) {
+    m.xikl[p] = b[2 * S.Q + p];
+    m.J[p] = b[2 * S.Q + S.npairs + p];
+  }
+  m.hmax = -1.0;
+  set_model_constants(m);
+  sub_latch = -1;
+  params_dirty = true;
+}
+
+// The variants' blocks [nvar][col_vars_stride] (rad/ns) to the device, and the Gershgorin row bounds maximised over the variants at the
+// control vector alpha: what ONE plan for all of them is made from (neumann_split choice, stand-in gate, kappa2).  The handle's own
+// constants and parameters are what they were on return.
+int qd_handle::variants_upload(int nvar, const double* blocks, const double* alpha) {
+  QD_HIP(qd::use_device(device));
+  const size_t n = (size_t)nvar * col_vars_stride(S.Q, S.npairs);
+  vars_host.assign(blocks, blocks + n);
+  int r;
+  if ((r = d_vconst.ensure(n))) return r;
+  QD_HIP(hipMemcpy(d_vconst.p, vars_host.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  const ModelConstants own = model_constants_now();
+  const bool ecoef_keep = ecoef_valid, traj_keep = traj_valid;
+  const std::vector<double> keep = params;
+  if (ndesign) std::memcpy(params.data(), alpha, sizeof(double) * ndesign);
+  vars_bound = RowBound{0.0, 0.0, 0.0};
+  for (int j = 0; j < nvar; j++) {
+    point_at_variant(j);
+    double dg, of;
+    row_bounds(&dg, &of);
+    vars_bound.diag = std::max(vars_bound.diag, dg);
+    vars_bound.off = std::max(vars_bound.off, of);
+  }
+  params = keep;
+  set_model_constants(own);
+  ecoef_valid = ecoef_keep;  // (nothing has been built in between)
+  traj_valid = traj_keep;
   return QD_OK;
 }
 
@@ -653,11 +735,12 @@ extern "C" int qd_eval_controls(qd_handle* h, const double* times, int nt, doubl
 // element table (once per handle) and work vectors (per batch size) of the large-state variant
 int qd_handle::ensure_big(int nb) {
   int r;
-  if (!d_ecoef.p) {
+  if (!ecoef_valid) {  // (once per handle - and again where the model constants have been swapped, set_model_constants)
     if ((r = d_ecoef.ensure((size_t)2 * S.dim)) || (r = d_edig.ensure((size_t)S.dim))) return r;
     QD_HIP(launch_big_table(S, d_ecoef.p, reinterpret_cast<unsigned*>(d_edig.p), stream));
     S.ecoef = d_ecoef.p;
     S.edig = reinterpret_cast<const unsigned*>(d_edig.p);
+    ecoef_valid = true;
   }
   if ((r = d_work.ensure(big_work_doubles(S, nb)))) return r;
   S.work = d_work.p;
@@ -1069,6 +1152,11 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
       set_gauge_tab(a, d_gauge.p, 0u);
     }
   }
+  if (sets && vars_tab) {  // a model-parameter ensemble on the lean column kernels: set j of the launch reads the block of variant batch_first + j
+    if (p.family != Family::Col || p.cfg.gmres || !p.neumann_split || S.dense)
+      return fail(QD_ERR_STATE, "model-parameter ensemble: only the diagonal-split stationary iteration of the lean column kernels sweeps several variants at once");
+    set_col_vars_tab(a, vars_tab + (size_t)batch_first * col_vars_stride(S.Q, S.npairs));
+  }
   a.cs = h->cs;
   a.nsub = h->nsub;
   a.nstages = h->nstages;
@@ -1108,7 +1196,7 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
-  if (sets && (!p.sweeps_sets(opts) || p.team != 1 || nb % sets != 0))
+  if (sets && ((!p.sweeps_sets(opts) && !vars_tab) || p.team != 1 || nb % sets != 0))
     return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state (standard model or user Hamiltonian) - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
@@ -1155,7 +1243,10 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
     // (nb_set: the instantiations with one control table per set - a missing one is an error, never another kernel)
     case Family::F32: return a.nb_set ? launch_sweep_f32_sets(a, adjoint, opts, st) : launch_sweep_f32(a, adjoint, opts, st);
     case Family::Slot: return a.nb_set ? launch_sweep_lean64_sets(a, adjoint, opts, st) : launch_sweep_lean64(a, adjoint, opts, st);
-    case Family::Col: return a.nb_set ? launch_sweep_col_sets(a, adjoint, st) : launch_sweep_col(a, adjoint, st);
+    // (a constants table: the third form, one block of model constants per set - qd_col_vars.h)
+    case Family::Col:
+      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_col_vars(a, adjoint, st);
+      return a.nb_set ? launch_sweep_col_sets(a, adjoint, st) : launch_sweep_col(a, adjoint, st);
     default:  // General and Global: the variant says which; nb_set: the instantiations with one control table per set
       if (a.nb_set) return adjoint ? launch_adjoint_sets(a, plan.cfg, st) : launch_forward_sets(a, plan.cfg, st);
       return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);
@@ -1209,6 +1300,10 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   if (a.ztraj) ztraj_fmt = plan.stage_layout();
   take_kernel(0);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 0))) return r;
+  if (a.sched && sets && vars_tab) {  // a sliced launch of the variants form carries its penalty sums from slice to slice
+    if ((r = d_pencarry.ensure((size_t)nb * COL_VARS_PEN_STRIDE))) return r;
+    set_col_vars_pen_carry(a, d_pencarry.p);
+  }
   QD_HIP(launch_sweep(a, plan, false, opts, stream));
   last_kernel[0] = take_kernel(0);
   QD_HIP(hipEventRecord(ev1, stream));

@@ -1,6 +1,7 @@
 // Host-side state behind the opaque qd_handle (one per GPU, single-threaded like the reference's
 // TimeStepper/MasterEq objects).  Internal; the public boundary is include/quandary_amd.h.
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -8,6 +9,7 @@
 
 #include <rccl/rccl.h>
 
+#include "qd_col_vars.h"
 #include "qd_gauge.h"
 #include "qd_internal.h"
 
@@ -28,6 +30,15 @@ inline hipError_t use_device(int device) {
   const hipError_t e = hipSetDevice(device);
   (void)hipGetLastError();
   return e;
+}
+
+// GHz -> rad/ns of the standard model's constants (src/mastereq.cpp:14-60): THE conversion - qd_create uses it for the handle's system,
+// the model-parameter ensemble for its variants, so that a variant has the bits a handle created with its constants would have
+inline double model_detune(double transfreq_ghz, double rotfreq_ghz) { return 2.0 * M_PI * (transfreq_ghz - rotfreq_ghz); }
+inline double model_kerr(double ghz) { return 2.0 * M_PI * ghz; }
+inline double model_coupling(double ghz) {  // threshold of Jkl_coupling (mastereq.hpp:633)
+  const double j = 2.0 * M_PI * ghz;
+  return std::fabs(j) > 1e-10 ? j : 0.0;
 }
 
 hipError_t launch_observables(const DevSys& S, const double* traj, int f32, int nb, int nstages, int stride, int nout, int nlev_total,
@@ -266,6 +277,24 @@ struct qd_handle {
   const double* ens_g0 = nullptr;
   size_t ens_g0_set() const { return (size_t)2 * S.N * S.N; }
   int ensemble_upload(int nvar, const double* hsys_re, const double* hsys_im, std::vector<double>& norms);  // norms: rowsum_max per variant
+  // Model-parameter ensemble (qd_optim_evalF_ensemble_model / qd_optim_evalGradF_ensemble_model): one control vector, nvar variants of the
+  // standard model's constants.  vars_host holds their blocks [nvar][col_vars_stride] in rad/ns (qd_col_vars.h; model_constants makes
+  // them what qd_create would), d_vconst the device copy.  While vars_tab is set a batch on the lean column family reads variant j's
+  // block for set j (prepare_sweep, launch_sweep: k_*_col_vars), and batch_begin takes vars_bound - the row bounds maximised over the
+  // variants - in place of the handle's own: one plan for all of them.  The fallback points the handle at one variant after the other
+  // (point_at_variant); ModelConstants is what it swaps and what the caller's scope restores.
+  std::vector<double> rotfreq;  // GHz, as given to qd_create (a variant keeps the rotating frame)
+  struct ModelConstants { double detune[QD_MAX_OSC], xi[QD_MAX_OSC], xikl[QD_MAX_PAIRS], J[QD_MAX_PAIRS]; double hmax; };
+  ModelConstants model_constants_now() const;
+  void set_model_constants(const ModelConstants& m);  // S and everything derived from it: the cached level-energy bound, the element table of the global-memory kernels
+  void point_at_variant(int j);
+  bool ecoef_valid = false;  // d_ecoef / d_edig belong to the current constants (ensure_big)
+  std::vector<double> vars_host;
+  qd::DBuf d_vconst;
+  qd::DBuf d_pencarry;  // penalty sums carried between the time slices of such a launch (qd_col_vars.h)
+  const double* vars_tab = nullptr;
+  qd::RowBound vars_bound{};
+  int variants_upload(int nvar, const double* blocks, const double* alpha);  // d_vconst, vars_host and vars_bound (at the control vector alpha)
   size_t batch_ctl_set() const { return sched_t.size() * (size_t)cs; }    // rows the step table really has x cs
   size_t batch_etable_set() const { return etimes.size() * (size_t)cs; }
   const double* batch_table() const { return d_btable.p + (size_t)batch_first * batch_ctl_set(); }

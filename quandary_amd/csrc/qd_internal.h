@@ -175,6 +175,8 @@ struct TuneOpts {
   int neumann_split = -1;  // "neumann_split": diagonal-split Neumann iteration (-1 = where it pays, 0 = never, 1 = wherever it is built)
   int batch_lean = 0;      // "batch_lean": the parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch) also shares launches on the lean slot,
                            // fp32-mixed and lean column families where their solver is a stationary iteration (0 = those go set by set, the default; 1 = one launch)
+  int ensemble_loop = 0;   // "ensemble_loop": a model-parameter ensemble (qd_optim_evalF_ensemble_model / qd_optim_evalGradF_ensemble_model) goes variant by
+                           // variant even where the lean column kernels could share its launches (A/B switch; 0 = share, the default)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
   double sched_wait_s = 0.0;    // "sched_wait_s": seconds a time slice may wait for its predecessor (0 = automatic: 4 s x the processes that share the
                                 // device (QD_DEVICE_SHARERS, set by the launchers that put several ranks on one GPU) x the slice length in units of 1000 steps)
@@ -282,6 +284,11 @@ hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose
 // the second where S.hasJ.
 hipError_t launch_sweep_col_sets(const SweepArgs& a, bool adjoint, hipStream_t st);
 hipError_t launch_sweep_colj_sets(const SweepArgs& a, bool adjoint, hipStream_t st);
+// ... with one block of model constants per set as well (qd_col_vars.hip / qd_colj_vars.hip: k_*_col_vars, k_*_colj_vars; the table of
+// qd_col_vars.h): the diagonal-split stationary instantiations only - a Krylov or plain-Neumann request is an error.  The first forwards
+// to the second where S.hasJ.
+hipError_t launch_sweep_col_vars(const SweepArgs& a, bool adjoint, hipStream_t st);
+hipError_t launch_sweep_colj_vars(const SweepArgs& a, bool adjoint, hipStream_t st);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false);
 size_t krylov_doubles(const DevSys& S, int nb);
 size_t big_work_doubles(const DevSys& S, int nb);

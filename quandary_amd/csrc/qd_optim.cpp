@@ -1024,6 +1024,9 @@ struct EnsembleCall {
   const double* w;                   // quadrature weights [nvar]
   const std::vector<double>* norms;  // Gershgorin row sum of every variant's Hsys
   double* grad_mean;                 // [ndesign] (gradient mode): sum_j w[j] grads[j]
+  // variants of the standard model's constants instead (qd_optim_eval(Grad)F_ensemble_model; norms is null): the caller has uploaded
+  // their blocks (qd_handle::variants_upload, vars_tab) - launches are shared on the lean column kernels' third form only
+  bool model = false;
 };
 
 // the regularisation terms of a gradient, on the host (src/optimproblem.cpp:356-372)
@@ -1063,7 +1066,10 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
     const SweepPlan plan = h->plan_sweep(nl, false);
     // (fp32-mixed is a family of its own: trajectory, stages and replicas follow the handle's precision, qd_handle::traj_doubles)
     // (grid.y of the per-set kernels; SweepArgs::ctl_set and gtab_set are 32 bits wide)
-    bool concurrent = plan.sweeps_sets(h->opts) && plan.team == 1 && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
+    // (a model-parameter ensemble: the diagonal-split stationary iteration of the lean column family - k_*_col_vars - whatever batch_lean says)
+    const bool shares = ens && ens->model ? plan.family == Family::Col && plan.cfg.gmres == 0 && plan.neumann_split && !h->opts.ensemble_loop
+                                          : plan.sweeps_sets(h->opts);
+    bool concurrent = shares && plan.team == 1 && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
                       nset <= 65535 && h->batch_ctl_set() <= 0xffffffffull && h->batch_gtab_set() <= 0xffffffffull;
     if (concurrent) {
       // a user Hamiltonian: the G(t) tables of the sets of one launch together stay within what qd_set_hamiltonian allows one table
@@ -1154,7 +1160,9 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
   for (int j = 0; j < nset; j++) {
     const double* alpha = alphas + (size_t)j * nd;
     double* grad = !grad_mode ? nullptr : grads ? grads + (size_t)j * nd : gone.data();
-    if (ens) {  // the handle as qd_set_hamiltonian would leave it for this variant: its G0, its row sum, the stand-in gates undecided
+    if (ens && ens->model) {  // the handle as qd_create would have made it for this variant (the caller's scope restores its own)
+      h->point_at_variant(j);
+    } else if (ens) {  // the handle as qd_set_hamiltonian would leave it for this variant: its G0, its row sum, the stand-in gates undecided
       h->ens_g0 = h->d_eg0.p + (size_t)j * h->ens_g0_set();
       h->dense_hsys_norm = (*ens->norms)[j];
       h->sub_latch = -1;
@@ -1248,6 +1256,98 @@ extern "C" int qd_optim_evalGradF_ensemble(qd_optim* o, const double* alpha, int
                                            const double* weights, qd_objective_value* vals, qd_objective_value* mean, double* grads,
                                            double* grad_mean) {
   return ensemble_eval(o, alpha, nvar, hsys_re, hsys_im, weights, true, vals, mean, grads, grad_mean, "qd_optim_evalGradF_ensemble");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Model-parameter ensemble: ONE control vector on nvar variants of the STANDARD model - transition frequencies, self-Kerr and
+// cross-Kerr coefficients, dipole-dipole couplings (GHz, NULL = the handle's own for every variant) - the weighted mean of their
+// objectives and gradients.  Variant j is the system of a handle created from the same qd_system with those arrays replaced;
+// rotation frequencies (eta, the control table), level counts, T1/T2, controls, target, penalties and initial conditions stay.
+// Where the plan's sweep is a diagonal-split stationary iteration of the lean column family the variants share launches: batch_eval
+// with the control vector replicated and k_*_col_vars / k_*_colj_vars reading variant j's constants from the table of qd_col_vars.h
+// (qd_handle::variants_upload; one plan from the largest row bounds among the variants).  Everything else - the other families,
+// Krylov or plain-Neumann column plans, chunked shards, option ensemble_loop - goes variant by variant through the single evaluation
+// with the handle pointed at one variant after the other (qd_handle::point_at_variant).
+// ---------------------------------------------------------------------------------------------------------------
+// leaves the handle on its own constants, plan latch and derived tables however the call ends
+struct ModelScope {
+  qd_handle* h;
+  qd_handle::ModelConstants own;
+  int latch_saved;
+  explicit ModelScope(qd_handle* hh) : h(hh), own(hh->model_constants_now()), latch_saved(hh->sub_latch) {}
+  ~ModelScope() {
+    h->vars_tab = nullptr;
+    h->set_model_constants(own);
+    h->sub_latch = latch_saved;  // (the stand-in gates of the handle's own system: not what the variants' bounds decided)
+    h->params_dirty = true;
+    h->traj_valid = false;
+  }
+};
+
+static int ensemble_model_eval(qd_optim* o, const double* alpha, int nvar, const double* transfreq, const double* selfkerr, const double* crosskerr,
+                               const double* Jkl, const double* weights, bool grad_mode, qd_objective_value* vals, qd_objective_value* mean,
+                               double* grads, double* grad_mean, const char* who) {
+  if (!o || nvar < 1 || !mean || (grad_mode && !grad_mean) || (!alpha && o->h->ndesign > 0))
+    return fail(QD_ERR_INVALID, std::string(who) + ": null argument or nvar < 1");
+  if (o->nranks != 1) return fail(QD_ERR_STATE, std::string(who) + ": single-rank entry point");
+  qd_handle* h = o->h;
+  if (h->S.dense) return fail(QD_ERR_STATE, std::string(who) + ": a user-Hamiltonian handle has no model constants (its variants go through qd_optim_evalF_ensemble / qd_optim_evalGradF_ensemble)");
+  std::vector<double> w(nvar, 1.0 / nvar);
+  if (weights) w.assign(weights, weights + nvar);
+  for (double wj : w)
+    if (!(wj >= 0.0) || !std::isfinite(wj)) return fail(QD_ERR_INVALID, std::string(who) + ": a weight is negative or not finite");
+  const int nd = h->ndesign, Q = h->S.Q, np = h->S.npairs, stride = col_vars_stride(Q, np);
+  // the variants' blocks in rad/ns, by the conversion of qd_create (qd_handle.h)
+  std::vector<double> blocks((size_t)nvar * stride);
+  for (int j = 0; j < nvar; j++) {
+    double* b = blocks.data() + (size_t)j * stride;
+    for (int k = 0; k < Q; k++) {
+      b[k] = transfreq ? model_detune(transfreq[(size_t)j * Q + k], h->rotfreq[k]) : h->S.detune[k];
+      b[Q + k] = selfkerr ? model_kerr(selfkerr[(size_t)j * Q + k]) : h->S.xi[k];
+    }
+    for (int p = 0; p < np; p++) {
+      b[2 * Q + p] = crosskerr ? model_kerr(crosskerr[(size_t)j * np + p]) : h->S.xikl[p];
+      b[2 * Q + np + p] = Jkl ? model_coupling(Jkl[(size_t)j * np + p]) : h->S.J[p];
+      if (!h->S.hasJ && b[2 * Q + np + p] != 0.0 && std::isfinite(b[2 * Q + np + p]))
+        return fail(QD_ERR_UNSUPPORTED, std::string(who) + ": a variant has a dipole-dipole coupling but the handle's system has none (its kernels carry no coupling terms): create the handle with a coupling");
+    }
+    for (int i = 0; i < stride; i++)
+      if (!std::isfinite(b[i])) return fail(QD_ERR_INVALID, std::string(who) + ": a model constant is not finite");
+  }
+  int r;
+  std::vector<double> alphas((size_t)nvar * nd);
+  std::vector<qd_objective_value> own(vals ? 0 : nvar);
+  if (!vals) vals = own.data();
+  for (int j = 0; j < nvar; j++) std::copy(alpha, alpha + nd, alphas.begin() + (size_t)j * nd);
+  ModelScope ms(h);
+  if ((r = h->variants_upload(nvar, blocks.data(), alpha))) return r;
+  h->vars_tab = h->d_vconst.p;
+  h->sub_latch = -1;
+  EnsembleCall ens{w.data(), nullptr, grad_mean};
+  ens.model = true;
+  if ((r = batch_eval(o, alphas.data(), nvar, grad_mode, vals, grads, who, &ens))) return r;
+  double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = 0; j < nvar; j++) {
+    const double v[8] = {vals[j].objective, vals[j].cost, vals[j].regul, vals[j].penalty, vals[j].penalty_dpdm, vals[j].penalty_energy,
+                         vals[j].penalty_variation, vals[j].fidelity};
+    for (int k = 0; k < 8; k++) m[k] = std::fma(w[j], v[k], m[k]);
+  }
+  *mean = qd_objective_value{m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]};
+  return QD_OK;
+}
+
+extern "C" int qd_optim_evalF_ensemble_model(qd_optim* o, const double* alpha, int nvar, const double* transfreq, const double* selfkerr,
+                                             const double* crosskerr, const double* Jkl, const double* weights, qd_objective_value* vals,
+                                             qd_objective_value* mean) {
+  return ensemble_model_eval(o, alpha, nvar, transfreq, selfkerr, crosskerr, Jkl, weights, false, vals, mean, nullptr, nullptr,
+                             "qd_optim_evalF_ensemble_model");
+}
+
+extern "C" int qd_optim_evalGradF_ensemble_model(qd_optim* o, const double* alpha, int nvar, const double* transfreq, const double* selfkerr,
+                                                 const double* crosskerr, const double* Jkl, const double* weights, qd_objective_value* vals,
+                                                 qd_objective_value* mean, double* grads, double* grad_mean) {
+  return ensemble_model_eval(o, alpha, nvar, transfreq, selfkerr, crosskerr, Jkl, weights, true, vals, mean, grads, grad_mean,
+                             "qd_optim_evalGradF_ensemble_model");
 }
 
 extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_batch_sets : QD_ERR_INVALID; }
