@@ -23,7 +23,12 @@ same call under ensemble_loop = 1 (variant by variant on one handle) and against
 created with its variant's constants before the clock starts.  Variant j: every transition frequency + j x 0.1 MHz, self- and cross-Kerr
 coefficients (and J_kl) x (1 + j x 1e-4).  The figure to hold it against is the parameter-set batch of the same set count (c4pure /
 c4diag / c4jpure): a variants launch should cost what that costs, plus the re-derivation per task.
-usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 m320pure m320diag m320j ...] > profiles/param_batch_probe.txt"""
+m22 / m16 / m27: the same call with option ensemble_general = 1 on the systems of e22 / e16 / e27 as standard-model specs (2x2
+Schroedinger, 4x4 and 3x3x3 Lindblad, 1000 steps of 0.004 ns; 4 / 4 / 3 one-workgroup states per variant) - the shared launches of
+k_forward_vars / k_adjoint_vars against the same call under ensemble_loop = 1, which is what a build without the option runs, and against
+the e22 / e16 / e27 lines.  Variant j: every constant x (1 + j x 1e-3).  single_spread_ms is the distance between the two consecutive
+single calls of a line: what the nvar 1 ensemble time has to be within, against the single time.
+usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 m320pure m320diag m320j m22 m16 m27 ...] > profiles/param_batch_probe.txt"""
 import os
 import sys
 import time
@@ -98,40 +103,47 @@ def ensemble_probe(which):
         h.close()
 
 
-MODEL = {"m320pure": "c4pure", "m320diag": "c4diag", "m320j": "c4jpure"}
+MODEL = {"m320pure": "c4pure", "m320diag": "c4diag", "m320j": "c4jpure", "m22": "d22", "m16": "d16", "m27": "d27"}
+GENERAL = ("m22", "m16", "m27")  # on the general kernel family: option ensemble_general, variants 0.1 % apart
 
 
-def model_variant(sp, j):
-    """The system block of variant j (a copy: the spec keeps its own)."""
+def model_variant(sp, j, rel=None):
+    """The system block of variant j (a copy: the spec keeps its own).  rel: every constant x (1 + j rel) instead."""
     s = type(sp.system).from_buffer_copy(sp.system)
     Q = s.nosc
     for k in range(Q):
-        s.transfreq[k] += 1e-4 * j
-        s.selfkerr[k] *= 1.0 + 1e-4 * j
+        s.transfreq[k] = s.transfreq[k] + 1e-4 * j if rel is None else s.transfreq[k] * (1.0 + rel * j)
+        s.selfkerr[k] *= 1.0 + (1e-4 if rel is None else rel) * j
     for i in range(Q * (Q - 1) // 2):
-        s.crosskerr[i] *= 1.0 + 1e-4 * j
-        s.Jkl[i] *= 1.0 + 1e-4 * j
+        s.crosskerr[i] *= 1.0 + (1e-4 if rel is None else rel) * j
+        s.Jkl[i] *= 1.0 + (1e-4 if rel is None else rel) * j
     return s
 
 
 def model_probe(which):
     workload, precision, options, nvars, overrides = PROBES[MODEL[which]]
+    general = which in GENERAL
+    rel = 1e-3 if general else None
+    if general:  # the standard model of the same system: no user Hamiltonian
+        overrides = {k: v for k, v in overrides.items() if k != "synthetic_hamiltonian_seed"}
     for grad in (True, False):
         def spec():
             return workload_spec(workload, "gradient" if grad else "simulation", overrides)
         sp = spec()
         h, hl = capi.Handle(sp), capi.Handle(sp)
+        if general:
+            h.set_option("ensemble_general", "1")
         hl.set_option("ensemble_loop", "1")
         o, ol = capi.Optim(h, sp), capi.Optim(hl, sp)
         pairs = []
         for j in range(max(nvars)):  # the comparator's handles: created with variant j's constants, outside the timed region
             spj = spec()
-            spj.system = model_variant(sp, j)
+            spj.system = model_variant(sp, j, rel)
             hj = capi.Handle(spj)
             pairs.append((hj, capi.Optim(hj, spj)))
         alpha = sp.params0
         for nvar in nvars:
-            variants = [model_variant(sp, j) for j in range(nvar)]
+            variants = [model_variant(sp, j, rel) for j in range(nvar)]
             if grad:
                 forms = (("ensemble", lambda: o.evalGradF_ensemble_model(alpha, variants, per_variant=False)),
                          ("loop", lambda: ol.evalGradF_ensemble_model(alpha, variants, per_variant=False)),
@@ -153,7 +165,8 @@ def model_probe(which):
             print(which, "grad" if grad else "fwd", "ninit", sp.ninit, "ntime", sp.time.ntime, "nvar", nvar, "variants_per_launch", sets,
                   "ensemble_ms", " ".join("%.2f" % v for v in t["ensemble"]), "loop_ms", " ".join("%.2f" % v for v in t["loop"]),
                   "single_ms", " ".join("%.2f" % v for v in t["single"]), "loop_over_ensemble %.2f" % (l / b),
-                  "single_over_ensemble %.2f" % (s / b), "ensemble_ms_per_variant %.3f" % (b / nvar), kern, flush=True)
+                  "single_over_ensemble %.2f" % (s / b), "ensemble_ms_per_variant %.3f" % (b / nvar),
+                  "single_spread_ms %.3f" % abs(t["single"][0] - t["single"][1]), kern, flush=True)
         for hj, oj in pairs:
             oj.close()
             hj.close()

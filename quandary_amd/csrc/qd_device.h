@@ -345,6 +345,20 @@ __device__ __forceinline__ void load_step_k(const double* row, StepC<Q>& c, bool
   }
 }
 
+// Where a matrix-free stencil takes the constants of the standard model that a model-parameter ensemble varies: transition frequencies
+// (detune), self-Kerr, cross-Kerr and dipole-dipole coupling, rad/ns.  VARS = false: the handle's, from the DevSys of the kernel
+// argument, as the stencils always read them.  VARS = true (k_forward_vars / k_adjoint_vars): the block of the workgroup's variant in a
+// device table, through the scalar path - that specialisation and the table's layout: qd_gen_vars.h / qd_col_vars.h.
+template <int Q, bool VARS>
+struct ModelK;
+template <int Q>
+struct ModelK<Q, false> {
+  __device__ __forceinline__ double detune(const DevSys& S, int k) const { return S.detune[k]; }
+  __device__ __forceinline__ double xi(const DevSys& S, int k) const { return S.xi[k]; }
+  __device__ __forceinline__ double xikl(const DevSys& S, int p) const { return S.xikl[p]; }
+  __device__ __forceinline__ double J(const DevSys& S, int p) const { return S.J[p]; }
+};
+
 // Moves a wave-uniform double from vector to scalar registers.
 __device__ __forceinline__ double to_scalar(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
@@ -478,8 +492,9 @@ constexpr int packed_digit_bits(int q) { return q <= 4 ? 8 : q == 5 ? 6 : q == 6
 // ---------------------------------------------------------------------------------------------
 // general stencil (runtime level counts)
 // ---------------------------------------------------------------------------------------------
-template <int Q, bool LIND, int EPT, bool HOIST_ = (EPT == 1) || (!LIND && EPT == 4)>
+template <int Q, bool LIND, int EPT, bool HOIST_ = (EPT == 1) || (!LIND && EPT == 4), bool VARS = false>
 struct GenStencil {
+  ModelK<Q, VARS> mc;  // source of detune / xi / xikl / J (no data unless VARS)
   static constexpr bool WHOLE = false;  // apply() works one slot at a time
   static constexpr bool NEEDS_SLOTS = false;  // apply() reads every neighbour from LDS
   static constexpr int DB = packed_digit_bits(Q);  // bits per packed digit
@@ -535,15 +550,15 @@ struct GenStencil {
       int pair = 0;
 #pragma unroll
       for (int k = 0; k < Q; k++) {
-        hd += S.detune[k] * ia[k] - S.xi[k] / 2.0 * ia[k] * (ia[k] - 1);
+        hd += mc.detune(S, k) * ia[k] - mc.xi(S, k) / 2.0 * ia[k] * (ia[k] - 1);
         if (LIND) {
-          hdp += S.detune[k] * ipa[k] - S.xi[k] / 2.0 * ipa[k] * (ipa[k] - 1);
+          hdp += mc.detune(S, k) * ipa[k] - mc.xi(S, k) / 2.0 * ipa[k] * (ipa[k] - 1);
           d += S.g2[k] * (ia[k] * ipa[k] - 0.5 * (ia[k] * ia[k] + ipa[k] * ipa[k])) - S.g1[k] / 2.0 * (ia[k] + ipa[k]);
         }
 #pragma unroll
         for (int l = k + 1; l < Q; l++) {
-          hd -= S.xikl[pair] * ia[k] * ia[l];
-          if (LIND) hdp -= S.xikl[pair] * ipa[k] * ipa[l];
+          hd -= mc.xikl(S, pair) * ia[k] * ia[l];
+          if (LIND) hdp -= mc.xikl(S, pair) * ipa[k] * ipa[l];
           pair++;
         }
       }
@@ -677,7 +692,7 @@ struct GenStencil {
       for (int k = 0; k < Q; k++) {
 #pragma unroll
         for (int l = k + 1; l < Q; l++, pair++) {
-          const double Jkl = S.J[pair];
+          const double Jkl = mc.J(S, pair);
           if (Jkl == 0.0) continue;
           const int a = dig(db, k), b = dig(db, l);
           const int sk = S.post[k], sl = S.post[l];
@@ -793,7 +808,7 @@ struct GenStencil {
         for (int u = 0; u < CH; u++) {
           if (p0 + u >= Q * (Q - 1) / 2) break;
           const int pair = p0 + u, k = pk[pair], l = pl[pair];
-          const double Jkl = S.J[pair];
+          const double Jkl = mc.J(S, pair);
           const int a = dig(db, k), b = dig(db, l);
           const double s1 = L.tdn[ofs[k] + a] * L.tup[ofs[l] + b], s2 = L.tdn[ofs[l] + b] * L.tup[ofs[k] + a];
           double ar = s1 * x1[u].x - s2 * x2[u].x, ai = s1 * x1[u].y - s2 * x2[u].y;  // T1 - T2
@@ -843,8 +858,9 @@ __device__ __forceinline__ double flip_if(double v, unsigned cond) {  // cond ? 
   return __hiloint2double(__double2hiint(v) ^ (int)(cond << 31), __double2loint(v));
 }
 
-template <int Q, bool LIND, int EPT>
+template <int Q, bool LIND, int EPT, bool VARS = false>
 struct QubitStencil {
+  ModelK<Q, VARS> mc;
   static constexpr bool WHOLE = false;
   static constexpr bool NEEDS_SLOTS = false;
   int it[EPT];
@@ -878,16 +894,16 @@ struct QubitStencil {
 #pragma unroll
       for (int k = 0; k < Q; k++) {
         const int a = (it[j] >> (Q - 1 - k)) & 1, ap = LIND ? (it[j] >> (2 * Q - 1 - k)) & 1 : 0;
-        hd += S.detune[k] * a;  // the self-Kerr term a(a-1) vanishes for two levels
+        hd += mc.detune(S, k) * a;  // the self-Kerr term a(a-1) vanishes for two levels
         if (LIND) {
-          hdp += S.detune[k] * ap;
+          hdp += mc.detune(S, k) * ap;
           d += S.g2[k] * (a * ap - 0.5 * (a + ap)) - S.g1[k] / 2.0 * (a + ap);
         }
 #pragma unroll
         for (int l = k + 1; l < Q; l++) {
           const int b = (it[j] >> (Q - 1 - l)) & 1, bp = LIND ? (it[j] >> (2 * Q - 1 - l)) & 1 : 0;
-          hd -= S.xikl[pair] * a * b;
-          if (LIND) hdp -= S.xikl[pair] * ap * bp;
+          hd -= mc.xikl(S, pair) * a * b;
+          if (LIND) hdp -= mc.xikl(S, pair) * ap * bp;
           pair++;
         }
       }
@@ -1012,7 +1028,7 @@ struct QubitStencil {
       for (int k = 0; k < Q; k++) {
 #pragma unroll
         for (int l = k + 1; l < Q; l++, pair++) {
-          const double Jkl = S.J[pair];
+          const double Jkl = mc.J(S, pair);
           const unsigned a = (i0 >> (Q - 1 - k)) & 1, b = (i0 >> (Q - 1 - l)) & 1;
           const double2 xj = sx[i0 ^ ((1 << (Q - 1 - k)) | (1 << (Q - 1 - l)))];
           const double mb = (a != b) ? 1.0 : 0.0;
@@ -1066,8 +1082,9 @@ struct QubitStencil {
 // PACKED (N <= 32): floor(64 / N) columns share one wave, lane = (column within the wave slot) N + row.  The ket
 // side is then uniform per lane group instead of per wave (plain vector arithmetic instead of scalars),
 // and only the bra neighbours of the stride-1 oscillator still come from registers (adjacent lanes).
-template <int Q, int EPT, bool PACKED = false>
+template <int Q, int EPT, bool PACKED = false, bool VARS = false>
 struct ColStencil {
+  ModelK<Q, VARS> mc;
   static constexpr bool WHOLE = false;
   static constexpr bool NEEDS_SLOTS = true;  // apply() takes the thread's other elements of the vector being read
   static constexpr int DB = packed_digit_bits(Q);
@@ -1136,13 +1153,13 @@ struct ColStencil {
       int pair = 0;
 #pragma unroll
       for (int k = 0; k < Q; k++) {
-        hd += S.detune[k] * ia[k] - S.xi[k] / 2.0 * ia[k] * (ia[k] - 1);
-        hdp += S.detune[k] * ipa[k] - S.xi[k] / 2.0 * ipa[k] * (ipa[k] - 1);
+        hd += mc.detune(S, k) * ia[k] - mc.xi(S, k) / 2.0 * ia[k] * (ia[k] - 1);
+        hdp += mc.detune(S, k) * ipa[k] - mc.xi(S, k) / 2.0 * ipa[k] * (ipa[k] - 1);
         d += S.g2[k] * (ia[k] * ipa[k] - 0.5 * (ia[k] * ia[k] + ipa[k] * ipa[k])) - S.g1[k] / 2.0 * (ia[k] + ipa[k]);
 #pragma unroll
         for (int l = k + 1; l < Q; l++) {
-          hd -= S.xikl[pair] * ia[k] * ia[l];
-          hdp -= S.xikl[pair] * ipa[k] * ipa[l];
+          hd -= mc.xikl(S, pair) * ia[k] * ia[l];
+          hdp -= mc.xikl(S, pair) * ipa[k] * ipa[l];
           pair++;
         }
       }
@@ -1216,7 +1233,7 @@ struct ColStencil {
       for (int k = 0; k < Q; k++) {
 #pragma unroll
         for (int l = k + 1; l < Q; l++, pair++) {
-          const double Jkl = S.J[pair];
+          const double Jkl = mc.J(S, pair);
           if (Jkl == 0.0) continue;
           const unsigned db = opaque(dbra);
           const int a = dig(db, k), b = dig(db, l);
@@ -1265,9 +1282,10 @@ struct ColStencil {
 //   * the LDS offset of a neighbour is a thread invariant plus an immediate slot offset,
 //   * the ket neighbours of oscillators 0 and 1 are the thread's OWN other slots (registers, no LDS).
 // ---------------------------------------------------------------------------------------------
-template <int Q>
+template <int Q, bool VARS = false>
 struct QubitSlotStencil {
   static_assert(Q >= 2, "needs two oscillators for the slot bits");
+  ModelK<Q, VARS> mc;
   static constexpr bool WHOLE = false;
   static constexpr bool NEEDS_SLOTS = true;
   static constexpr int EPT = 4;
@@ -1296,14 +1314,14 @@ struct QubitSlotStencil {
 #pragma unroll
       for (int k = 0; k < Q; k++) {
         const int a = (it[j] >> brabit(k)) & 1, ap = (it[j] >> ketbit(k)) & 1;
-        hd += S.detune[k] * a;
-        hdp += S.detune[k] * ap;
+        hd += mc.detune(S, k) * a;
+        hdp += mc.detune(S, k) * ap;
         d += S.g2[k] * (a * ap - 0.5 * (a + ap)) - S.g1[k] / 2.0 * (a + ap);
 #pragma unroll
         for (int l = k + 1; l < Q; l++) {
           const int b = (it[j] >> brabit(l)) & 1, bp = (it[j] >> ketbit(l)) & 1;
-          hd -= S.xikl[pair] * a * b;
-          hdp -= S.xikl[pair] * ap * bp;
+          hd -= mc.xikl(S, pair) * a * b;
+          hdp -= mc.xikl(S, pair) * ap * bp;
           pair++;
         }
       }
@@ -1402,7 +1420,7 @@ struct QubitSlotStencil {
       for (int k = 0; k < Q; k++) {
 #pragma unroll
         for (int l = k + 1; l < Q; l++, pair++) {
-          const double Jkl = S.J[pair];
+          const double Jkl = mc.J(S, pair);
           const unsigned a = (i0 >> brabit(k)) & 1, b = (i0 >> brabit(l)) & 1;
           const double2 xj = sx[i0 ^ ((1 << brabit(k)) | (1 << brabit(l)))];
           const double mb = (a != b) ? 1.0 : 0.0;
@@ -1821,33 +1839,34 @@ struct DenseMfma32Stencil : DenseStencil<Q, true, 4> {
   }
 };
 
-template <int Q, bool LIND, int EPT, bool QUBIT, bool COL = false, bool DENSE = false, bool PACKED = false, bool MFMA = false>
-struct StencilSel { typedef GenStencil<Q, LIND, EPT> type; };
+// (VARS: the standard-model stencils with the constants of a variant, ModelK - never a dense one)
+template <int Q, bool LIND, int EPT, bool QUBIT, bool COL = false, bool DENSE = false, bool PACKED = false, bool MFMA = false, bool VARS = false>
+struct StencilSel { typedef GenStencil<Q, LIND, EPT, (EPT == 1) || (!LIND && EPT == 4), VARS> type; };
+template <int Q, bool LIND, int EPT, bool VARS>
+struct StencilSel<Q, LIND, EPT, true, false, false, false, false, VARS> { typedef QubitStencil<Q, LIND, EPT, VARS> type; };
+template <int Q, int EPT, bool PACKED, bool VARS>
+struct StencilSel<Q, true, EPT, false, true, false, PACKED, false, VARS> { typedef ColStencil<Q, EPT, PACKED, VARS> type; };
+template <int Q, bool VARS>
+struct StencilSel<Q, true, 4, true, false, false, false, false, VARS> { typedef QubitSlotStencil<Q, VARS> type; };
 template <int Q, bool LIND, int EPT>
-struct StencilSel<Q, LIND, EPT, true, false, false, false, false> { typedef QubitStencil<Q, LIND, EPT> type; };
-template <int Q, int EPT, bool PACKED>
-struct StencilSel<Q, true, EPT, false, true, false, PACKED, false> { typedef ColStencil<Q, EPT, PACKED> type; };
+struct StencilSel<Q, LIND, EPT, false, false, true, false, false, false> { typedef DenseStencil<Q, LIND, EPT> type; };
 template <int Q>
-struct StencilSel<Q, true, 4, true, false, false, false, false> { typedef QubitSlotStencil<Q> type; };
-template <int Q, bool LIND, int EPT>
-struct StencilSel<Q, LIND, EPT, false, false, true, false, false> { typedef DenseStencil<Q, LIND, EPT> type; };
+struct StencilSel<Q, true, 4, false, false, true, false, true, false> { typedef DenseMfmaStencil<Q> type; };
 template <int Q>
-struct StencilSel<Q, true, 4, false, false, true, false, true> { typedef DenseMfmaStencil<Q> type; };
-template <int Q>
-struct StencilSel<Q, true, 4, false, false, true, true, true> { typedef DenseMfma32Stencil<Q> type; };
+struct StencilSel<Q, true, 4, false, false, true, true, true, false> { typedef DenseMfma32Stencil<Q> type; };
 
 template <typename ST, typename = void> struct has_split_fetch { static constexpr bool value = false; };
 template <typename ST> struct has_split_fetch<ST, decltype((void)ST::SPLIT_FETCH)> { static constexpr bool value = ST::SPLIT_FETCH; };
 
 template <typename ST> __device__ __forceinline__ bool slot_valid(const ST& st, int j);
-template <int Q, bool LIND, int EPT, bool HOIST>
-__device__ __forceinline__ bool slot_valid(const GenStencil<Q, LIND, EPT, HOIST>& st, int j) { return st.valid[j]; }
-template <int Q, bool LIND, int EPT>
-__device__ __forceinline__ bool slot_valid(const QubitStencil<Q, LIND, EPT>& st, int j) { return st.valid[j]; }
-template <int Q, int EPT, bool PACKED>
-__device__ __forceinline__ bool slot_valid(const ColStencil<Q, EPT, PACKED>& st, int j) { return st.valid[j]; }
-template <int Q>
-__device__ __forceinline__ bool slot_valid(const QubitSlotStencil<Q>& st, int j) { return st.valid[j]; }
+template <int Q, bool LIND, int EPT, bool HOIST, bool VARS>
+__device__ __forceinline__ bool slot_valid(const GenStencil<Q, LIND, EPT, HOIST, VARS>& st, int j) { return st.valid[j]; }
+template <int Q, bool LIND, int EPT, bool VARS>
+__device__ __forceinline__ bool slot_valid(const QubitStencil<Q, LIND, EPT, VARS>& st, int j) { return st.valid[j]; }
+template <int Q, int EPT, bool PACKED, bool VARS>
+__device__ __forceinline__ bool slot_valid(const ColStencil<Q, EPT, PACKED, VARS>& st, int j) { return st.valid[j]; }
+template <int Q, bool VARS>
+__device__ __forceinline__ bool slot_valid(const QubitSlotStencil<Q, VARS>& st, int j) { return st.valid[j]; }
 template <int Q, bool LIND, int EPT, bool HOIST>
 __device__ __forceinline__ bool slot_valid(const DenseStencil<Q, LIND, EPT, HOIST>& st, int j) { return st.valid[j]; }
 template <int Q>
@@ -1990,11 +2009,11 @@ __device__ __forceinline__ void finalizeJ_diff(const DevTarget& tg, double re, d
 // ---------------------------------------------------------------------------------------------
 // GM: the GMRES code paths are compiled in (separate kernel instantiations, so that the Neumann kernels do
 // not pay for them in registers and code size)
-template <int Q, bool LIND, int VAR, bool QUBIT, bool GM = false>
+template <int Q, bool LIND, int VAR, bool QUBIT, bool GM = false, bool VARS = false>
 struct Team {
   typedef Variant<VAR> V;
   static constexpr int EPT = V::EPT;  // slots per thread
-  typedef typename StencilSel<Q, LIND, EPT, QUBIT, V::COL, V::DENSE, V::PACKED, V::MFMA>::type ST;
+  typedef typename StencilSel<Q, LIND, EPT, QUBIT, V::COL, V::DENSE, V::PACKED, V::MFMA, VARS>::type ST;
   ST st;
   Lds L;
   int cur;      // which LDS buffer holds the vector that may be stencil-read
@@ -2640,187 +2659,18 @@ __device__ __forceinline__ const double* sweep_gtab(const SweepArgs& A, const De
 
 // SETS: parameter-set batch - the states are sets of A.nb_set, each set with a control table of its own, A.ctl_set doubles apart
 // (qd_optim_evalGradF_batch); everything else is indexed by the state as in any batch.  false: one table, the kernels as they were.
+// VARS: model-parameter ensemble - the states are sets of A.nb_set as well, a set is a variant of the standard model's constants
+// (ModelK; k_forward_vars below) and every set reads the one control table.
 template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false, bool SETS = false>
 __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward(const SweepArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef Team<Q, LIND, VAR, QUBIT, GM> TM;
-  constexpr int EPT = TM::EPT;
-  const DevSys& S = A.S;
-  TM tm;
-  tm.init(S, smem, A.use_gmres);
-  const int dim = S.dim;
-  double2 x[EPT];
-#pragma unroll
-  for (int j = 0; j < EPT; j++) {
-    const double* x0 = A.x0 + (size_t)tm.ic0 * 2 * dim;
-    x[j] = make_double2(x0[tm.st.it[j]], x0[dim + tm.st.it[j]]);
-  }
-  team_sync<TM::V::ONEWAVE>();  // coefficient tables written by init()
-  tm.publish(x);
-  // penalty bookkeeping
-  const bool ee = PLAIN ? false : A.stepper_ee != 0;
-  const bool pen_on = PLAIN ? false : A.gamma_penalty > 1e-13;
-  const bool wj_on = pen_on && A.penalty_param > 1e-13;
-  // Schroedinger Jtrace is the only objective whose finalizeJ is nonlinear in the per-state sums:
-  // it needs a block reduction per step; everything else accumulates thread-locally.
-  const bool wj_reduce = wj_on && !LIND && A.tg.objective_type == QD_OBJ_JTRACE;
-  const bool dpdm_on = PLAIN ? false : (A.gamma_dpdm > 1e-13 && !LIND);
-  const bool jpairs = S.npairs > 0;
-  bool guard[EPT];
-#pragma unroll
-  for (int j = 0; j < EPT; j++) guard[j] = A.leak_on && tm.ok(j) && tm.st.is_guard(S, j);
-  double pen_local = 0.0, dpdm_local = 0.0, pen_uniform = 0.0;
-  double2 xm1[EPT], xm2[EPT];  // dpdm history (x_n, x_{n-1})
-#pragma unroll
-  for (int j = 0; j < EPT; j++) xm1[j] = xm2[j] = x[j];
-  unsigned long long napply = 0;
-  double* traj = A.traj;
-  const double dtinv4 = 1.0 / (A.dt * A.dt * A.dt * A.dt);
-  // latency-bound variants prefetch the next table row; the throughput variants (several waves per
-  // SIMD) load the row where it is used and keep it in scalar registers
-  constexpr bool PREFETCH = !TM::V::LEAN;
-  constexpr bool XSTASH = TM::V::LEAN;  // explicit staging of the state through L2/HBM instead of compiler spills
-  StepC<Q> c, cn;
-  if (PREFETCH) load_step<Q>(sweep_ctl<SETS>(A, tm.ic0), cn, jpairs);
-
-  vm_drain();
-  for (int s = 0; s < A.nsub; s++) {
-    if (PREFETCH) {
-      c = cn;
-      if (s + 1 < A.nsub) load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, cn, jpairs);  // prefetch the next row
-    } else {
-      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)s * A.cs, c, jpairs);
-      scalarize<Q>(c, jpairs);
-    }
-    c.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)s * S.N * S.N : nullptr;
-    tm.st.prep(S, tm.L, c);
-    if (traj) {
-#pragma unroll
-      for (int j = 0; j < EPT; j++)
-        if (tm.ok(j)) {
-          double* dst = traj + ((size_t)s * A.nb + tm.ic0) * 2 * dim;  // written once, read by the adjoint sweep much later:
-          __builtin_nontemporal_store(x[j].x, dst + tm.st.it[j]);        // streaming stores, the caches keep the solver's vectors
-          __builtin_nontemporal_store(x[j].y, dst + dim + tm.st.it[j]);
-        }
-    }
-    // rhs = M x   (ImplMidpoint::evolveFWD, timestepper.cpp:594; ExplEuler :502)
-    double2 rhs[EPT];
-    tm.template apply_all<false>(S, c, x, rhs);
-    napply++;
-    if (XSTASH && !ee) {  // x is not needed during the linear solve: park it in the output buffer
-#pragma unroll
-      for (int j = 0; j < EPT; j++)
-        if (tm.ok(j)) {
-          double* xs = A.xT + (size_t)tm.ic0 * 2 * dim;
-          const int e = at_use<EPT>(tm.st.it[j]);
-          xs[e] = x[j].x;
-          xs[dim + e] = x[j].y;
-        }
-    }
-    if (ee) {
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        x[j].x = fma(c.h, rhs[j].x, x[j].x);
-        x[j].y = fma(c.h, rhs[j].y, x[j].y);
-      }
-    } else {
-      double2 k[EPT];
-      napply += tm.template solve<false>(A, c, 0.5 * c.h, rhs, k);
-      if (XSTASH) {
-#pragma unroll
-        for (int j = 0; j < EPT; j++) {
-          const double* xs = A.xT + (size_t)tm.ic0 * 2 * dim;
-          const int e = at_use<EPT>(tm.st.it[j]);
-          x[j] = make_double2(xs[e], xs[dim + e]);
-        }
-      }
-      if (A.ztraj) {  // the primal stage z = x + h/2 k: read back by the adjoint sweep instead of repeating this solve
-#pragma unroll
-        for (int j = 0; j < EPT; j++)
-          if (tm.ok(j)) stage_store(A.ztraj, (size_t)s * A.nb + tm.ic0, dim, tm.st.it[j], fma(0.5 * c.h, k[j].x, x[j].x), fma(0.5 * c.h, k[j].y, x[j].y));
-      }
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        x[j].x = fma(c.h, k[j].x, x[j].x);
-        x[j].y = fma(c.h, k[j].y, x[j].y);
-      }
-    }
-    tm.publish(x);
-
-    // in-loop penalties, evaluated at the end of a FULL time step (timestepper.cpp:141-154)
-    if ((pen_on || dpdm_on) && (s + 1) % A.nstages == 0) {
-      const int n = (s + 1) / A.nstages - 1;  // step index n: state is x_{n+1}
-      const double tstop = (n + 1) * A.dt;
-      if (pen_on) {
-        double weight = 0.0;
-        if (wj_on) {
-          if (A.wjw) {  // tabulated per time step (qd_handle::ensure_wj_weights): no exp() next to the state registers
-            weight = to_scalar(A.wjw[n]);
-          } else {
-            const double a = (tstop - A.Tfinal) / A.penalty_param;
-            weight = 1.0 / A.penalty_param * exp(-(a * a));
-          }
-        }
-        if (wj_reduce) {
-          double v[2] = {0.0, 0.0};
-#pragma unroll
-          for (int j = 0; j < EPT; j++)
-            if (tm.ok(j)) evalJ_part<LIND>(S, A.tg, tm.ic0, at_use<EPT>(tm.st.it[j]), x[j], v[0], v[1]);
-          tm.template sum<2>(v);
-          pen_uniform += weight * finalizeJ<LIND>(A.tg, v[0], v[1]) * A.dt;
-        } else if (wj_on) {
-#pragma unroll
-          for (int j = 0; j < EPT; j++)
-            if (tm.ok(j)) {
-              double jr = 0.0, ji = 0.0;
-              evalJ_part<LIND>(S, A.tg, tm.ic0, at_use<EPT>(tm.st.it[j]), x[j], jr, ji);
-              // finalizeJ is affine here: J = jr (Jfrobenius, Jmeasure) or 1 - jr (Lindblad Jtrace)
-              pen_local += (A.tg.objective_type == QD_OBJ_JTRACE ? -1.0 : 1.0) * weight * A.dt * jr;
-            }
-          if (A.tg.objective_type == QD_OBJ_JTRACE) pen_uniform += weight * A.dt;
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; j++)
-          if (guard[j]) pen_local += (x[j].x * x[j].x + x[j].y * x[j].y) / A.ntime;
-      }
-      if (dpdm_on) {
-        if (n > 0) {
-#pragma unroll
-          for (int j = 0; j < EPT; j++)
-            if (tm.ok(j)) {
-              const double t1 = x[j].x * x[j].x - 2.0 * xm1[j].x * xm1[j].x + xm2[j].x * xm2[j].x;
-              const double t2 = x[j].y * x[j].y - 2.0 * xm1[j].y * xm1[j].y + xm2[j].y * xm2[j].y;
-              dpdm_local += dtinv4 * (t1 + t2) * (t1 + t2);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; j++) {
-          xm2[j] = xm1[j];
-          xm1[j] = x[j];
-        }
-      }
-    }
-  }
-  // final state (+ last trajectory slot)
-#pragma unroll
-  for (int j = 0; j < EPT; j++)
-    if (tm.ok(j)) {
-      double* xT = A.xT + (size_t)tm.ic0 * 2 * dim;
-      xT[tm.st.it[j]] = x[j].x;
-      xT[dim + tm.st.it[j]] = x[j].y;
-      if (traj) {
-        double* dst = traj + ((size_t)A.nsub * A.nb + tm.ic0) * 2 * dim;
-        dst[tm.st.it[j]] = x[j].x;
-        dst[dim + tm.st.it[j]] = x[j].y;
-      }
-    }
-  double v[2] = {pen_local, dpdm_local};
-  tm.template sum<2>(v);
-  if (threadIdx.x == 0) {
-    A.pen_out[tm.ic0] = v[0] + pen_uniform;
-    A.dpdm_out[tm.ic0] = v[1] / A.ntime;
-    atomicAdd(A.napply, napply);
-  }
+  constexpr bool VARS = false;
+#include "qd_forward_body.h"
+}
+// the third form: the template arguments of the kernel a single evaluation runs on
+template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false>
+__global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward_vars(const SweepArgs A) {
+  constexpr bool SETS = false, VARS = true;
+#include "qd_forward_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2831,305 +2681,13 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward(const SweepArgs 
 // ---------------------------------------------------------------------------------------------
 template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false, bool SETS = false>
 __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef Team<Q, LIND, VAR, QUBIT, GM> TM;
-  constexpr int EPT = TM::EPT;
-  const DevSys& S = A.S;
-  TM tm;
-  tm.init(S, smem, A.use_gmres);
-  team_sync<TM::V::ONEWAVE>();
-  const int dim = S.dim;
-  double2 xb[EPT], xn[EPT];  // adjoint state, primal state x_n (end of the step being reversed)
-  const double* traj = A.traj;
-  auto load_state = [&](int s, double2(&dst)[EPT]) {
-#pragma unroll
-    for (int j = 0; j < EPT; j++) {
-      const double* src = traj + ((size_t)s * A.nb + tm.ic0) * 2 * dim;
-      dst[j] = make_double2(__builtin_nontemporal_load(src + tm.st.it[j]), __builtin_nontemporal_load(src + dim + tm.st.it[j]));
-    }
-  };
-#pragma unroll
-  for (int j = 0; j < EPT; j++) {
-    const double* xbT = A.xbarT + (size_t)tm.ic0 * 2 * dim;
-    xb[j] = make_double2(xbT[tm.st.it[j]], xbT[dim + tm.st.it[j]]);
-  }
-  const bool jpairs = S.npairs > 0;
-  const bool ee = PLAIN ? false : A.stepper_ee != 0;
-  if (ee && !LIND) {
-    // Schroedinger runs of the reference do not store the forward states: the adjoint loop re-computes the primal
-    // backwards with the FORWARD stepper and a negative step, xprimal <- xprimal + (tstart - tstop) M(tstop) xprimal
-    // (src/timestepper.cpp:229-231 with ExplEuler::evolveFWD :496-507), and so do the dpdm states (:207-211, :236-243).
-    // That is exact for the symmetric IMR family but O(dt) away from the forward states for explicit Euler, and the
-    // reference's EE gradient is defined on this backward chain.  Reproduce it: overwrite the stored trajectory with
-    // the chain x_N, B_N x_N, B_{N-1} B_N x_N, ... (every thread only touches its own elements), then run the
-    // ordinary adjoint loop on it.
-    double* trajw = const_cast<double*>(traj);
-    double2 xp[EPT];
-    load_state(A.nsub, xp);
-    for (int s = A.nsub - 1; s >= 0; s--) {
-      StepC<Q> c1;
-      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, c1, jpairs);  // M(tstop of step s) = row s + 1
-      if (TM::V::LEAN) scalarize<Q>(c1, jpairs);
-      c1.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)(s + 1) * S.N * S.N : nullptr;
-      tm.st.prep(S, tm.L, c1);
-      const double hneg = -sweep_ctl<SETS>(A, tm.ic0)[(size_t)s * A.cs];
-      tm.publish(xp);
-      double2 t[EPT];
-      tm.template apply_all<false>(S, c1, xp, t);
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        xp[j].x = fma(hneg, t[j].x, xp[j].x);
-        xp[j].y = fma(hneg, t[j].y, xp[j].y);
-        if (tm.ok(j)) {
-          double* dst = trajw + ((size_t)s * A.nb + tm.ic0) * 2 * dim;
-          const int e = at_use<EPT>(tm.st.it[j]);
-          dst[e] = xp[j].x;
-          dst[dim + e] = xp[j].y;
-        }
-      }
-    }
-    __threadfence_block();
-    team_sync<TM::V::ONEWAVE>();
-  }
-  // Latency-bound variants (few elements per thread) carry x_{n+1} in registers and prefetch x_{n-1} one
-  // step ahead; the throughput variants re-read them (L2 / HBM) to keep the register footprint small.
-  constexpr bool CARRY = !TM::V::LEAN && !PLAIN;  // (PLAIN: nothing in the sweep reads the primal states)
-  if (CARRY) load_state(A.nsub, xn);
-  const int bq = min(tm.ic0, A.nb - 1);
-  const double jbar_pen = A.jbar[bq * 3 + 0], jbar_dpdm = A.jbar[bq * 3 + 1];
-  const bool pen_on = PLAIN ? false : A.gamma_penalty > 1e-13;
-  const bool wj_on = pen_on && A.penalty_param > 1e-13;
-  const bool wj_reduce = wj_on && !LIND && A.tg.objective_type == QD_OBJ_JTRACE;
-  const bool dpdm_on = PLAIN ? false : (A.gamma_dpdm > 1e-13 && !LIND);
-  bool guard[EPT];
-#pragma unroll
-  for (int j = 0; j < EPT; j++) guard[j] = A.leak_on && tm.ok(j) && tm.st.is_guard(S, j);
-  const double dtinv4 = 1.0 / (A.dt * A.dt * A.dt * A.dt);
-  const int ntime = A.ntime;
-  double2 x[EPT], xnext[CARRY ? EPT : 1];
-  if (CARRY) load_state(A.nsub - 1, reinterpret_cast<double2(&)[EPT]>(xnext));  // primal at the start of the last sub-step
-  // Latency-bound variants: the primal stage z and the control row of sub-step s - 1 are fetched while sub-step s is being reversed.
-  // Loaded where they are used, each costs a full global / scalar memory round trip on the critical path of EVERY step of a sweep
-  // that is nothing but one dependent chain per initial condition.
-  constexpr bool ZAHEAD = !TM::V::LEAN;
-  double2 znext[ZAHEAD ? EPT : 1];
-  StepC<Q> cn;
-  auto load_stage = [&](int ss, double2(&dst)[ZAHEAD ? EPT : 1]) {
-#pragma unroll
-    for (int j = 0; j < (ZAHEAD ? EPT : 0); j++) dst[j] = stage_load(A.ztraj, (size_t)ss * A.nb + tm.ic0, dim, tm.st.it[j]);
-  };
-  if (ZAHEAD && !ee && A.nsub > 0) {
-    load_stage(A.nsub - 1, znext);
-    load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(A.nsub - 1) * A.cs, cn, jpairs);
-  }
-
-  vm_drain();
-  for (int s = A.nsub - 1; s >= 0; s--) {
-    if (CARRY) {
-#pragma unroll
-      for (int j = 0; j < EPT; j++) x[j] = xnext[CARRY ? j : 0];
-      if (s > 0) load_state(s - 1, reinterpret_cast<double2(&)[EPT]>(xnext));
-    } else if (ee) {
-      load_state(s, x);
-    }
-    // ---- penalty adjoints at the end of a full step, using the primal x_n (timestepper.cpp:220-227)
-    if ((pen_on || dpdm_on) && (s + 1) % A.nstages == 0) {
-      const int n = (s + 1) / A.nstages;
-      const double tstop = n * A.dt;
-      if (!CARRY) load_state(s + 1, xn);
-      if (dpdm_on) {  // penaltyDpDm_diff (timestepper.cpp:372-442); all five states come from HBM
-        double2 m2[EPT], m1[EPT], p1[EPT], p2[EPT];
-        if (n > 1) load_state((n - 2) * A.nstages, m2);
-        if (n > 0) load_state((n - 1) * A.nstages, m1);
-        if (n < ntime) load_state((n + 1) * A.nstages, p1);
-        if (n < ntime - 1) load_state((n + 2) * A.nstages, p2);
-#pragma unroll
-        for (int j = 0; j < EPT; j++) {
-          const double Jb = jbar_dpdm / ntime;
-          const double xr = xn[j].x, xi = xn[j].y;
-          double acc = 0.0;
-          if (n > 1) {
-            const double t1 = m2[j].x * m2[j].x - 2.0 * m1[j].x * m1[j].x + xr * xr;
-            const double t2 = m2[j].y * m2[j].y - 2.0 * m1[j].y * m1[j].y + xi * xi;
-            acc += 2.0 * (t1 + t2);
-          }
-          if (n > 0 && n < ntime) {
-            const double t1 = m1[j].x * m1[j].x - 2.0 * xr * xr + p1[j].x * p1[j].x;
-            const double t2 = m1[j].y * m1[j].y - 2.0 * xi * xi + p1[j].y * p1[j].y;
-            acc += -4.0 * (t1 + t2);
-          }
-          if (n < ntime - 1) {
-            const double t1 = xr * xr - 2.0 * p1[j].x * p1[j].x + p2[j].x * p2[j].x;
-            const double t2 = xi * xi - 2.0 * p1[j].y * p1[j].y + p2[j].y * p2[j].y;
-            acc += 2.0 * (t1 + t2);
-          }
-          xb[j].x += acc * 2.0 * xr * dtinv4 * Jb;
-          xb[j].y += acc * 2.0 * xi * dtinv4 * Jb;
-        }
-      }
-      if (pen_on) {  // penaltyIntegral_diff (timestepper.cpp:300-339)
-        if (wj_on) {
-          double weight;
-          if (A.wjw) {
-            weight = to_scalar(A.wjw[n - 1]);
-          } else {
-            const double a = (tstop - A.Tfinal) / A.penalty_param;
-            weight = 1.0 / A.penalty_param * exp(-(a * a));
-          }
-          double rb, ib;
-          if (wj_reduce) {
-            double v[2] = {0.0, 0.0};
-#pragma unroll
-            for (int j = 0; j < EPT; j++)
-              if (tm.ok(j)) evalJ_part<LIND>(S, A.tg, tm.ic0, at_use<EPT>(tm.st.it[j]), xn[j], v[0], v[1]);
-            tm.template sum<2>(v);
-            finalizeJ_diff<LIND>(A.tg, v[0], v[1], rb, ib);
-          } else {
-            finalizeJ_diff<LIND>(A.tg, 0.0, 0.0, rb, ib);
-          }
-#pragma unroll
-          for (int j = 0; j < EPT; j++)
-            if (tm.ok(j))
-              evalJ_diff_elem<LIND>(S, A.tg, tm.ic0, at_use<EPT>(tm.st.it[j]), xn[j], xb[j], weight * rb * jbar_pen * A.dt,
-                                    weight * ib * jbar_pen * A.dt);
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; j++)
-          if (guard[j]) {
-            xb[j].x += 2.0 * xn[j].x * jbar_pen / ntime;
-            xb[j].y += 2.0 * xn[j].y * jbar_pen / ntime;
-          }
-      }
-    }
-    StepC<Q> c;
-    double2 znow[ZAHEAD ? EPT : 1];
-    if (ZAHEAD && !ee) {
-      c = cn;
-#pragma unroll
-      for (int j = 0; j < (ZAHEAD ? EPT : 0); j++) znow[j] = znext[j];
-      if (s > 0) {
-        load_stage(s - 1, znext);
-        load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s - 1) * A.cs, cn, jpairs);
-      }
-    } else {
-      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)s * A.cs, c, jpairs);
-    }
-    if (TM::V::LEAN) scalarize<Q>(c, jpairs);
-    c.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)s * S.N * S.N : nullptr;
-    tm.st.prep(S, tm.L, c);
-    double cf[2 * Q];
-#pragma unroll
-    for (int i = 0; i < 2 * Q; i++) cf[i] = 0.0;
-    // (the coefficient sums are completed behind the barrier that publishes the next vector: store_coeffs, tm.publish, collect_coeffs)
-    auto coeff_dst = [&](int g) -> double* { return A.coeff + ((size_t)tm.ic0 * A.nsub + s) * 2 * Q + g; };
-    auto store_coeffs = [&]() { tm.template sum_store_post<2 * Q>(cf, coeff_dst); };
-    auto collect_coeffs = [&]() { tm.template sum_store_collect<2 * Q>(coeff_dst); };
-    if (ee) {
-      // ExplEuler::evolveBWD (timestepper.cpp:506-520): gradient with dt * x_adj against x_{n-1}, then
-      // x_adj += dt M(tstop)^T x_adj.  The table row of sub-step s holds M(tstart); M(tstop) is row s+1
-      // (the last row is followed by one extra row for t = T).
-      tm.publish(x);
-#pragma unroll
-      for (int j = 0; j < EPT; j++)
-        if (tm.ok(j)) {
-#pragma unroll
-          for (int k = 0; k < Q; k++) {
-            double2 Av, Bv;
-            tm.st.ladder(S, tm.L, tm.vec(), k, j, Av, Bv);
-            cf[2 * k] += c.h * (Bv.y * xb[j].x - Bv.x * xb[j].y);
-            cf[2 * k + 1] += c.h * (Av.x * xb[j].x + Av.y * xb[j].y);
-          }
-        }
-      store_coeffs();
-      StepC<Q> c1;
-      load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(s + 1) * A.cs, c1, jpairs);
-      c1.g = S.dense ? reinterpret_cast<const double2*>(sweep_gtab<SETS>(A, S, tm.ic0)) + (size_t)(s + 1) * S.N * S.N : nullptr;
-      tm.st.prep(S, tm.L, c1);
-      tm.publish(xb);
-      collect_coeffs();
-      double2 t[EPT];
-      tm.template apply_all<true>(S, c1, xb, t);
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        xb[j].x = fma(c.h, t[j].x, xb[j].x);
-        xb[j].y = fma(c.h, t[j].y, xb[j].y);
-      }
-    } else {
-      // ImplMidpoint::evolveBWD (timestepper.cpp:631-694).  The reference repeats the forward solve of the sub-step to get the
-      // primal stage z = x + h/2 k (:640-652); here the forward sweep has stored z next to the trajectory (SweepArgs::ztraj,
-      // the same solve on the same data: identical values), so only the adjoint solve remains and neither x nor z is alive
-      // while it runs.
-      double2 kb[EPT];  // adjoint stage: (I - h/2 M)^T kbar = xbar ; kbar *= h
-      tm.template solve<true>(A, c, 0.5 * c.h, xb, kb);
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        kb[j].x *= c.h;
-        kb[j].y *= c.h;
-      }
-      double2 z[EPT];
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        if (ZAHEAD) {
-          z[j] = znow[ZAHEAD ? j : 0];
-        } else {
-          z[j] = stage_load(A.ztraj, (size_t)s * A.nb + tm.ic0, dim, tm.st.it[j]);
-        }
-      }
-      tm.publish(z);
-      // gradient coefficients: x^T dM/dp_k z and x^T dM/dq_k z with x := kbar
-      if constexpr (TM::ST::WHOLE) {  // matrix-core stencils: the commutators of all the thread's elements at once per oscillator
-        typename TM::ST::ZOps zo;
-        tm.st.ladder_fetch(tm.vec(), zo);
-#pragma unroll
-        for (int k = 0; k < Q; k++) {
-          double2 Av[EPT], Bv[EPT];
-          tm.st.ladder_whole(S, zo, k, Av, Bv);
-#pragma unroll
-          for (int j = 0; j < EPT; j++)
-            if (tm.ok(j)) {
-              cf[2 * k] += Bv[j].y * kb[j].x - Bv[j].x * kb[j].y;
-              cf[2 * k + 1] += Av[j].x * kb[j].x + Av[j].y * kb[j].y;
-            }
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < EPT; j++)
-          if (tm.ok(j)) {
-#pragma unroll
-            for (int k = 0; k < Q; k++) {
-              double2 Av, Bv;
-              tm.st.ladder(S, tm.L, tm.vec(), k, j, Av, Bv);
-              cf[2 * k] += Bv.y * kb[j].x - Bv.x * kb[j].y;
-              cf[2 * k + 1] += Av.x * kb[j].x + Av.y * kb[j].y;
-            }
-          }
-      }
-      store_coeffs();
-      // xbar += M^T kbar
-      tm.publish(kb);
-      collect_coeffs();
-      double2 t[EPT];
-      tm.template apply_all<true>(S, c, kb, t);
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        xb[j].x += t[j].x;
-        xb[j].y += t[j].y;
-      }
-    }
-    if (CARRY) {
-#pragma unroll
-      for (int j = 0; j < EPT; j++) xn[j] = x[j];
-    }
-  }
-  if (A.xbar0) {
-#pragma unroll
-    for (int j = 0; j < EPT; j++)
-      if (tm.ok(j)) {
-        double* d0 = A.xbar0 + (size_t)tm.ic0 * 2 * dim;
-        d0[tm.st.it[j]] = xb[j].x;
-        d0[dim + tm.st.it[j]] = xb[j].y;
-      }
-  }
+  constexpr bool VARS = false;
+#include "qd_adjoint_body.h"
+}
+template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false>
+__global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint_vars(const SweepArgs A) {
+  constexpr bool SETS = false, VARS = true;
+#include "qd_adjoint_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------

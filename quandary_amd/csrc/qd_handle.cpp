@@ -1152,9 +1152,9 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
       set_gauge_tab(a, d_gauge.p, 0u);
     }
   }
-  if (sets && vars_tab) {  // a model-parameter ensemble on the lean column kernels: set j of the launch reads the block of variant batch_first + j
-    if (p.family != Family::Col || p.cfg.gmres || !p.neumann_split || S.dense)
-      return fail(QD_ERR_STATE, "model-parameter ensemble: only the diagonal-split stationary iteration of the lean column kernels sweeps several variants at once");
+  if (sets && vars_tab) {  // a model-parameter ensemble: set j of the launch reads the block of variant batch_first + j
+    if (!p.sweeps_vars(opts) || S.dense)
+      return fail(QD_ERR_STATE, "model-parameter ensemble: only the diagonal-split stationary iteration of the lean column kernels and, with option ensemble_general, the general kernel family with one workgroup per state sweep several variants at once");
     set_col_vars_tab(a, vars_tab + (size_t)batch_first * col_vars_stride(S.Q, S.npairs));
   }
   a.cs = h->cs;
@@ -1196,7 +1196,7 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
-  if (sets && ((!p.sweeps_sets(opts) && !vars_tab) || p.team != 1 || nb % sets != 0))
+  if (sets && (!(vars_tab ? p.sweeps_vars(opts) : p.sweeps_sets(opts)) || p.team != 1 || nb % sets != 0))
     return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state (standard model or user Hamiltonian) - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
@@ -1247,7 +1247,9 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
     case Family::Col:
       if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_col_vars(a, adjoint, st);
       return a.nb_set ? launch_sweep_col_sets(a, adjoint, st) : launch_sweep_col(a, adjoint, st);
-    default:  // General and Global: the variant says which; nb_set: the instantiations with one control table per set
+    default:  // General and Global: the variant says which; nb_set: the instantiations with one control table per set, or - a constants
+              // table - the third form, one block of model constants per set (qd_gen_vars.h)
+      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return adjoint ? launch_adjoint_vars(a, plan.cfg, st) : launch_forward_vars(a, plan.cfg, st);
       if (a.nb_set) return adjoint ? launch_adjoint_sets(a, plan.cfg, st) : launch_forward_sets(a, plan.cfg, st);
       return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);
   }

@@ -117,6 +117,12 @@ struct SweepPlan {
   bool sweeps_sets(const TuneOpts& o) const {
     return family == Family::General || (o.batch_lean && (family == Family::Slot || family == Family::F32 || family == Family::Col) && cfg.gmres == 0);
   }
+  // Kernels that read one block of model constants per set exist for this plan (model-parameter ensemble on a standard-model handle):
+  // the diagonal-split stationary iteration of the lean column family (k_*_col_vars), and under option ensemble_general the general
+  // family - Neumann and both direct Krylov forms (k_forward_vars / k_adjoint_vars)
+  bool sweeps_vars(const TuneOpts& o) const {
+    return (family == Family::Col && cfg.gmres == 0 && neumann_split) || (family == Family::General && o.ensemble_general);
+  }
 };
 
 }  // namespace qd

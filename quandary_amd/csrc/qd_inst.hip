@@ -6,8 +6,20 @@
 // SweepArgs::nb_set states (parameter-set batch, qd_optim_evalGradF_batch) - for the variants with one workgroup per state in LDS, of
 // the standard Hamiltonian model (QD_B = 0 | 1) and of the dense user Hamiltonians (QD_B = 2: variants 11, 12, 13, 15, 17, one G(t) table
 // per set as well, SweepArgs::gtab_set); no operator application, no global-memory kernels (variant 16).
+// With -DQD_VARS=1 (build/qd_vars_*.o): the third form, k_forward_vars / k_adjoint_vars - one block of model constants per set of
+// SweepArgs::nb_set states and one control table for all (model-parameter ensemble, qd_optim_evalGradF_ensemble_model; qd_gen_vars.h) -
+// for the same LDS variants of the standard Hamiltonian model only (QD_B = 0 | 1): no dense variants, no variant 16.
 #include "qd_device.h"
 #include "qd_big.h"
+#ifndef QD_VARS
+#define QD_VARS 0
+#endif
+#if QD_VARS
+#include "qd_gen_vars.h"
+#if QD_B == 2 || defined(QD_SETS)
+#error "QD_VARS: the standard Hamiltonian model only (QD_B = 0 | 1), and not together with QD_SETS"
+#endif
+#endif
 
 #if !defined(QD_Q) || !defined(QD_L) || !defined(QD_B) || !defined(QD_PART)
 #error "compile with -DQD_Q=<1..8> -DQD_L=<0|1> -DQD_B=<0 general|1 qubit|2 dense> -DQD_PART=<0 forward + apply|1 adjoint|2 forward, GMRES kernels|3 adjoint, GMRES kernels>"
@@ -19,6 +31,7 @@ constexpr bool kGmPart = (QD_PART >= 2);
 #define QD_SETS 0
 #endif
 constexpr bool kSets = (QD_SETS != 0);
+constexpr bool kVars = (QD_VARS != 0);
 
 namespace qd {
 
@@ -47,9 +60,23 @@ constexpr bool kLind = (QD_L != 0);
 #if QD_PART == 0 || QD_PART == 2
 template <int VAR>
 static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && !kSets && variant_built(QD_Q, kLind, QD_B, VAR)) {
+  if constexpr (VAR == 16 && !kSets && !kVars && variant_built(QD_Q, kLind, QD_B, VAR)) {
     note_kernel(0, "k_forward_big", QD_Q, kLind, kDense, kGmPart);
     return launch_big(reinterpret_cast<const void*>(k_forward_big<QD_Q, kLind, kDense, kGmPart>), a, cfg, st);
+#if QD_VARS
+  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
+    auto kf = k_forward_vars<QD_Q, kLind, VAR, kQubit, kGmPart, false>;
+    bool plain = false;
+    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
+      plain = plain_sweep(a, cfg, 0);
+      if (plain) kf = k_forward_vars<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+    }
+    hipError_t e = set_lds(kf, cfg.lds);
+    if (e != hipSuccess) return e;
+    note_kernel(0, "k_forward_vars", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
+    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
+    return hipGetLastError();
+#else
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, false, kSets>;
     bool plain = false;
@@ -63,12 +90,13 @@ static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     else note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
+#endif
   } else {
     return hipErrorInvalidValue;
   }
 }
 #endif
-#if QD_PART == 0 && !QD_SETS
+#if QD_PART == 0 && !QD_SETS && !QD_VARS
 template <int VAR>
 static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb,
                            const LaunchCfg& cfg, hipStream_t st) {
@@ -94,7 +122,7 @@ static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose,
 #if QD_PART == 1 || QD_PART == 3
 template <int VAR>
 static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && !kSets && variant_built(QD_Q, kLind, QD_B, VAR)) {
+  if constexpr (VAR == 16 && !kSets && !kVars && variant_built(QD_Q, kLind, QD_B, VAR)) {
     if constexpr (!kGmPart) {
       if (a.stepper_ee) {
         note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, false, true);
@@ -103,6 +131,20 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     }
     note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, kGmPart, false);
     return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, kGmPart, false>), a, cfg, st);
+#if QD_VARS
+  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
+    auto kf = k_adjoint_vars<QD_Q, kLind, VAR, kQubit, kGmPart, false>;
+    bool plain = false;
+    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
+      plain = plain_sweep(a, cfg, 1);
+      if (plain) kf = k_adjoint_vars<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+    }
+    hipError_t e = set_lds(kf, cfg.lds);
+    if (e != hipSuccess) return e;
+    note_kernel(1, "k_adjoint_vars", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
+    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
+    return hipGetLastError();
+#else
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
     auto kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, false, kSets>;
     bool plain = false;
@@ -116,6 +158,7 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     else note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
+#endif
   } else {
     return hipErrorInvalidValue;
   }
@@ -139,7 +182,12 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     default: return hipErrorInvalidValue;    \
   }
 
-#if QD_SETS
+#if QD_VARS
+#define QD_FWD inst_forwardvars_
+#define QD_FWDGM inst_forwardgmvars_
+#define QD_ADJ inst_adjointvars_
+#define QD_ADJGM inst_adjointgmvars_
+#elif QD_SETS
 #define QD_FWD inst_forwardsets_
 #define QD_FWDGM inst_forwardgmsets_
 #define QD_ADJ inst_adjointsets_
@@ -156,7 +204,7 @@ hipError_t QD_NAME(QD_FWD, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchCfg
   if (cfg.gmres) return QD_NAME(QD_FWDGM, QD_Q, QD_L, QD_B)(a, cfg, st);  // GMRES kernels: another object
   QD_VAR_SWITCH(go_forward, a, cfg, st)
 }
-#if !QD_SETS
+#if !QD_SETS && !QD_VARS
 hipError_t QD_NAME(inst_apply_, QD_Q, QD_L, QD_B)(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y,
                                                   int nb, const LaunchCfg& cfg, hipStream_t st) {
   QD_VAR_SWITCH(go_apply, S, ctlrow, transpose, x, y, nb, cfg, st)
@@ -177,7 +225,7 @@ hipError_t QD_NAME(QD_ADJGM, QD_Q, QD_L, QD_B)(const SweepArgs& a, const LaunchC
   QD_VAR_SWITCH(go_adjoint, a, cfg, st)
 }
 #endif
-#if QD_B == 0 && QD_PART == 0 && !QD_SETS
+#if QD_B == 0 && QD_PART == 0 && !QD_SETS && !QD_VARS
 hipError_t QD_NAME(inst_bigtable_, QD_Q, QD_L, QD_B)(const DevSys& S, double* ecoef, unsigned* edig, hipStream_t st) {
   hipLaunchKernelGGL((k_big_table<QD_Q, kLind>), dim3((S.dim + 255) / 256), dim3(256), 0, st, S, reinterpret_cast<double2*>(ecoef),
                      reinterpret_cast<uint2*>(edig));

@@ -175,6 +175,7 @@ struct TuneOpts {
   int neumann_split = -1;  // "neumann_split": diagonal-split Neumann iteration (-1 = where it pays, 0 = never, 1 = wherever it is built)
   int batch_lean = 0;      // "batch_lean": the parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch) also shares launches on the lean slot,
                            // fp32-mixed and lean column families where their solver is a stationary iteration (0 = those go set by set, the default; 1 = one launch)
+  int ensemble_general = 0;  // "ensemble_general": a model-parameter ensemble shares launches on the general kernel family too (k_forward_vars / k_adjoint_vars; 0 = variant by variant there)
   int ensemble_loop = 0;   // "ensemble_loop": a model-parameter ensemble (qd_optim_evalF_ensemble_model / qd_optim_evalGradF_ensemble_model) goes variant by
                            // variant even where the lean column kernels could share its launches (A/B switch; 0 = share, the default)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
@@ -231,6 +232,11 @@ hipError_t launch_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t 
 // Hamiltonian model and of the dense user Hamiltonians (one G(t) table per set, a.gtab_set)
 hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+// ... with one block of model constants per set of a.nb_set states and ONE control table (qd_inst.hip with -DQD_VARS=1: k_forward_vars /
+// k_adjoint_vars, the template arguments of the kernel launch_forward / launch_adjoint pick for the same arguments; the table of
+// qd_col_vars.h in a.S.hcr, qd_gen_vars.h): the LDS variants of the standard Hamiltonian model, Neumann and GMRES kernels
+hipError_t launch_forward_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+hipError_t launch_adjoint_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 // control tables of nset parameter vectors in one launch: params [nset][ndesign] -> table [nset][nrows][cs], table2 [nset][nrows2][cs]
 hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int ndesign, int nset, const double* times, const double* hs, int nrows,
                                 double* table, const double* times2, const double* hs2, int nrows2, double* table2, int cs,

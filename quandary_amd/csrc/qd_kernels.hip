@@ -625,7 +625,7 @@ size_t krylov_doubles(const DevSys& S, int nb) { return (size_t)nb * (GMRES_MR_G
 // options
 // ---------------------------------------------------------------------------------------------
 static const char* const kOptKeys[] = {"var", "force_neumann", "no_mfma", "big_team", "big_spread", "big_blocked", "lean64_sb", "no_lean64", "no_collean",
-                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "batch_lean", "ensemble_loop", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
+                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "batch_lean", "ensemble_loop", "ensemble_general", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
 int TuneOpts::set(const char* key, const char* value) {
   if (!key || !value) return -1;
   const std::string k(key), v(value);
@@ -670,6 +670,7 @@ int TuneOpts::set(const char* key, const char* value) {
   else if (k == "no_lean64") no_lean64 = iv != 0;
   else if (k == "batch_lean") batch_lean = iv != 0;
   else if (k == "ensemble_loop") ensemble_loop = iv != 0;
+  else if (k == "ensemble_general") ensemble_general = iv != 0;
   else if (k == "col_skip") col_skip = v == "auto" ? 1 : iv != 0;
   else if (k == "no_collean") no_collean = iv != 0;
   else if (k == "no_col_krylov") no_col_krylov = iv != 0;
@@ -766,6 +767,34 @@ hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStre
       (cfg.qubit == 2) != (a.S.dense != 0) || (a.S.dense && (!a.S.gtab || !a.gtab_set)) || !adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
     return hipErrorInvalidValue;
   return adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+}
+
+// the third form (qd_inst.hip with -DQD_VARS=1): one block of model constants per set, the table of qd_col_vars.h in a.S.hcr; the
+// standard Hamiltonian model only, index [qubit][lindblad][Q-1]
+#define QD_DECLV(q, l, b)                                                                        \
+  hipError_t inst_forwardvars_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t); \
+  hipError_t inst_adjointvars_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
+#define QD_DECLV_Q(l, b) QD_DECLV(1, l, b) QD_DECLV(2, l, b) QD_DECLV(3, l, b) QD_DECLV(4, l, b) QD_DECLV(5, l, b)
+QD_DECLV_Q(0, 0) QD_DECLV_Q(1, 0) QD_DECLV_Q(0, 1) QD_DECLV_Q(1, 1)
+QD_DECLV(6, 0, 0) QD_DECLV(7, 0, 0) QD_DECLV(8, 0, 0) QD_DECLV(6, 0, 1) QD_DECLV(7, 0, 1) QD_DECLV(8, 0, 1)
+QD_DECLV(6, 1, 0) QD_DECLV(7, 1, 0) QD_DECLV(8, 1, 0)
+static const sweep_fn fwd_vars_tab[2][2][8] = {{QD_ROW8(inst_forwardvars_, 0, 0), QD_ROW8(inst_forwardvars_, 1, 0)},
+                                               {QD_ROW8(inst_forwardvars_, 0, 1), QD_ROW(inst_forwardvars_, 1, 1)}};
+static const sweep_fn adj_vars_tab[2][2][8] = {{QD_ROW8(inst_adjointvars_, 0, 0), QD_ROW8(inst_adjointvars_, 1, 0)},
+                                               {QD_ROW8(inst_adjointvars_, 0, 1), QD_ROW(inst_adjointvars_, 1, 1)}};
+
+// a.nb states = a.nb / a.nb_set variants; a dense handle, variant 16, a missing table or a missing instantiation is an error
+static bool vars_args_ok(const SweepArgs& a, const LaunchCfg& cfg) {
+  return a.S.Q >= 1 && a.S.Q <= 8 && (cfg.qubit == 0 || cfg.qubit == 1) && cfg.var != 16 && a.nb_set >= 1 && a.nb % a.nb_set == 0 &&
+         !a.S.dense && a.S.hcr != nullptr && a.S.npairs == a.S.Q * (a.S.Q - 1) / 2;
+}
+hipError_t launch_forward_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (!vars_args_ok(a, cfg) || !fwd_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
+  return fwd_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+}
+hipError_t launch_adjoint_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (!vars_args_ok(a, cfg) || !adj_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
+  return adj_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
 }
 
 hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
