@@ -428,8 +428,15 @@ int qd_optim_evalGradF_ensemble(qd_optim* o, const double* alpha, int nvar, cons
  * workgroup per state in LDS, fp64: two to five coupled qubits or qutrits, Schroedinger or Lindblad, and the 3 x 20 class under
  * no_collean) - k_forward_vars / k_adjoint_vars, the workgroup of a state reading its variant's constants through scalar loads; a
  * neumann request, a gmres request on the Krylov kernels (basis in LDS or in global memory) and one served by the Neumann stand-in
- * alike.  With the default 0 that family goes variant by variant.  Every other
- * configuration - general (without the option), slot, fp32-mixed and global-memory families, plain-Neumann or Krylov column plans, chunked shards - goes
+ * alike.  With the default 0 that family goes variant by variant.
+ * Option ensemble_lean (qd_set_option; 0 = default, 1 = on): the variants share launches on the lean slot and fp32-mixed families as
+ * well (all-qubit Lindblad systems: 2^4 and 2^5 in fp64, 2x2x2, 2^4 and 2^5 in QD_PRECISION_F32MIXED, with or without dipole-dipole
+ * coupling) where the sweep's solver is a stationary iteration - a neumann request, or a gmres request served by the Neumann stand-in -
+ * on k_forward_q32_vars / k_adjoint_q32_vars, the workgroup of a state reading its variant's constants through scalar loads.  A Krylov
+ * plan (gmres_split = 0) goes variant by variant.  The uncoupled 2^5 system picks its elements per thread from all states of the launch
+ * (variants x initial conditions), as the parameter-set batch does: option lean64_sb pins it.  With the default 0 those families go
+ * variant by variant.  Every other
+ * configuration - general, slot and fp32-mixed (without their options), Krylov plans of the latter two, global-memory families, plain-Neumann or Krylov column plans, chunked shards - goes
  * variant by variant through the single evaluation with the handle pointed at one variant after the other: the numbers of a fresh
  * handle, qd_optim_last_batch_sets = 1.
  * After the call the state is that of a batch call; the handle's own constants, its solver latch and every table derived from them are
@@ -501,7 +508,8 @@ int qd_set_precision(qd_handle* h, int precision);
  * path of the lean kernels' Krylov solvers accepts at residual <= krylov_tau x the reference's tolerance, default 0.1), krylov_restart (restart length of those solvers' generic path, 1 .. 14), force_neumann, var (kernel variant), no_mfma,
  * no_lean64, lean64_sb, no_collean, no_col_krylov, col_min_n, big_team, big_spread, big_blocked, traj_budget_mb (double), batch_lean (the parameter-set
  * batch shares launches on the lean slot, fp32-mixed and lean column families too: see qd_optim_evalF_batch; 0 = default), ensemble_general (a model-parameter ensemble shares launches on the general kernel family too: see
- * qd_optim_evalF_ensemble_model; 0 = default), ensemble_loop (a model-parameter
+ * qd_optim_evalF_ensemble_model; 0 = default), ensemble_lean (... and on the stationary iterations of the lean slot and
+ * fp32-mixed families; 0 = default), ensemble_loop (a model-parameter
  * ensemble goes variant by variant even where it could share launches: see qd_optim_evalF_ensemble_model; 0 = default).  Every key is also read from the
  * environment variable QD_<KEY> once, at qd_create (tests, measurements).  Unknown keys: QD_ERR_INVALID. */
 int qd_set_option(qd_handle* h, const char* key, const char* value);

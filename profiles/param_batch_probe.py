@@ -28,7 +28,12 @@ Schroedinger, 4x4 and 3x3x3 Lindblad, 1000 steps of 0.004 ns; 4 / 4 / 3 one-work
 k_forward_vars / k_adjoint_vars against the same call under ensemble_loop = 1, which is what a build without the option runs, and against
 the e22 / e16 / e27 lines.  Variant j: every constant x (1 + j x 1e-3).  single_spread_ms is the distance between the two consecutive
 single calls of a line: what the nvar 1 ensemble time has to be within, against the single time.
-usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 m320pure m320diag m320j m22 m16 m27 ...] > profiles/param_batch_probe.txt"""
+mq4 / mc5 / mq3f32 / mq4j: the same call with option ensemble_lean = 1 on the lean slot and fp32-mixed families - 2^4 and 2^5 Lindblad in
+fp64 (the q4 / c5 workloads), 2x2x2 Lindblad in fp32-mixed (c2), the coupled 2^4 system (q4j) - from the three `3states` initial
+conditions over 1000 steps: three workgroups per variant on 256 CUs.  The shared launches of k_forward_q32_vars / k_adjoint_q32_vars
+against the same call under ensemble_loop = 1, alternating in one process.  Variant j: every constant x (1 + j x 1e-3).  loop_spread_ms is
+the distance between the two loop calls of a line: what one shared variant against a loop of one has to be read against.
+usage: param_batch_probe.py [c1 c3 q4 c5 c2f32 c4pure c4diag c4jpure c4jdiag d22 d16 d27 e22 e16 e27 m320pure m320diag m320j m22 m16 m27 mq4 mc5 mq3f32 mq4j ...] > profiles/param_batch_probe.txt"""
 import os
 import sys
 import time
@@ -105,6 +110,9 @@ def ensemble_probe(which):
 
 MODEL = {"m320pure": "c4pure", "m320diag": "c4diag", "m320j": "c4jpure", "m22": "d22", "m16": "d16", "m27": "d27"}
 GENERAL = ("m22", "m16", "m27")  # on the general kernel family: option ensemble_general, variants 0.1 % apart
+# on the lean slot / fp32-mixed families: option ensemble_lean, variants 0.1 % apart; name -> (workload, precision, nvar values, overrides)
+S3 = {"initialcondition": "3states"}
+LEAN = {"mq4": ("q4", "f64", COL, S3), "mc5": ("c5", "f64", COL, S3), "mq3f32": ("c2", "f32mixed", COL, S3), "mq4j": ("q4j", "f64", COL, S3)}
 
 
 def model_variant(sp, j, rel=None):
@@ -121,18 +129,26 @@ def model_variant(sp, j, rel=None):
 
 
 def model_probe(which):
-    workload, precision, options, nvars, overrides = PROBES[MODEL[which]]
+    lean = which in LEAN
+    if lean:
+        workload, precision, nvars, overrides = LEAN[which]
+    else:
+        workload, precision, options, nvars, overrides = PROBES[MODEL[which]]
     general = which in GENERAL
-    rel = 1e-3 if general else None
+    rel = 1e-3 if general or lean else None
     if general:  # the standard model of the same system: no user Hamiltonian
         overrides = {k: v for k, v in overrides.items() if k != "synthetic_hamiltonian_seed"}
     for grad in (True, False):
         def spec():
-            return workload_spec(workload, "gradient" if grad else "simulation", overrides)
+            sp = workload_spec(workload, "gradient" if grad else "simulation", overrides)
+            sp.precision = precision
+            return sp
         sp = spec()
         h, hl = capi.Handle(sp), capi.Handle(sp)
         if general:
             h.set_option("ensemble_general", "1")
+        if lean:
+            h.set_option("ensemble_lean", "1")
         hl.set_option("ensemble_loop", "1")
         o, ol = capi.Optim(h, sp), capi.Optim(hl, sp)
         pairs = []
@@ -166,7 +182,8 @@ def model_probe(which):
                   "ensemble_ms", " ".join("%.2f" % v for v in t["ensemble"]), "loop_ms", " ".join("%.2f" % v for v in t["loop"]),
                   "single_ms", " ".join("%.2f" % v for v in t["single"]), "loop_over_ensemble %.2f" % (l / b),
                   "single_over_ensemble %.2f" % (s / b), "ensemble_ms_per_variant %.3f" % (b / nvar),
-                  "single_spread_ms %.3f" % abs(t["single"][0] - t["single"][1]), kern, flush=True)
+                  "single_spread_ms %.3f" % abs(t["single"][0] - t["single"][1]), "loop_spread_ms %.3f" % abs(t["loop"][0] - t["loop"][1]),
+                  kern, flush=True)
         for hj, oj in pairs:
             oj.close()
             hj.close()
@@ -178,7 +195,7 @@ for which in (sys.argv[1:] or ["c1", "c3"]):
     if which in ENSEMBLE:
         ensemble_probe(which)
         continue
-    if which in MODEL:
+    if which in MODEL or which in LEAN:
         model_probe(which)
         continue
     workload, precision, options, nsets, overrides = PROBES[which]

@@ -649,8 +649,9 @@ class Optim:
         created from that system; every field of the mean is sum_j weights[j] x that field (weights as given, None = 1 / nvar each).
         The variants share sweep launches where the plan is a diagonal-split stationary iteration of the lean column kernels
         (last_batch_sets; option ensemble_loop = 1: variant by variant); with option ensemble_general = 1 they share launches on the general
-        kernel family too (k_forward_vars / k_adjoint_vars: small coupled systems, Neumann and Krylov kernels); everything else goes variant
-        by variant."""
+        kernel family too (k_forward_vars / k_adjoint_vars: small coupled systems, Neumann and Krylov kernels), with option ensemble_lean = 1
+        on the stationary iterations of the lean slot and fp32-mixed families (k_forward_q32_vars / k_adjoint_q32_vars: open systems of
+        three to five qubits); everything else goes variant by variant."""
         alpha, nvar, tf, sk, ck, jk, w = self._ensemble_model_args(alpha, variants, weights)
         vals = (qd_objective_value * max(nvar, 1))()
         mean = qd_objective_value()

@@ -1154,7 +1154,7 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   }
   if (sets && vars_tab) {  // a model-parameter ensemble: set j of the launch reads the block of variant batch_first + j
     if (!p.sweeps_vars(opts) || S.dense)
-      return fail(QD_ERR_STATE, "model-parameter ensemble: only the diagonal-split stationary iteration of the lean column kernels and, with option ensemble_general, the general kernel family with one workgroup per state sweep several variants at once");
+      return fail(QD_ERR_STATE, "model-parameter ensemble: only the diagonal-split stationary iteration of the lean column kernels, with option ensemble_general the general kernel family with one workgroup per state and, with option ensemble_lean, the stationary iterations of the lean slot and fp32-mixed families sweep several variants at once");
     set_col_vars_tab(a, vars_tab + (size_t)batch_first * col_vars_stride(S.Q, S.npairs));
   }
   a.cs = h->cs;
@@ -1196,7 +1196,9 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
-  if (sets && (!(vars_tab ? p.sweeps_vars(opts) : p.sweeps_sets(opts)) || p.team != 1 || nb % sets != 0))
+  if (sets && vars_tab && (!p.sweeps_vars(opts) || p.team != 1 || nb % sets != 0))
+    return fail(QD_ERR_STATE, "model-parameter ensemble: only the lean column kernels, the general kernel family (option ensemble_general) and the stationary iterations of the lean slot and fp32-mixed families (option ensemble_lean), one workgroup per state, sweep several variants at once");
+  if (sets && !vars_tab && (!p.sweeps_sets(opts) || p.team != 1 || nb % sets != 0))
     return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state (standard model or user Hamiltonian) - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
@@ -1241,9 +1243,13 @@ int qd_handle::arm_slices(qd::SweepArgs& a, int nb, int which) {
 static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool adjoint, const TuneOpts& opts, hipStream_t st) {
   switch (plan.family) {
     // (nb_set: the instantiations with one control table per set - a missing one is an error, never another kernel)
-    case Family::F32: return a.nb_set ? launch_sweep_f32_sets(a, adjoint, opts, st) : launch_sweep_f32(a, adjoint, opts, st);
-    case Family::Slot: return a.nb_set ? launch_sweep_lean64_sets(a, adjoint, opts, st) : launch_sweep_lean64(a, adjoint, opts, st);
-    // (a constants table: the third form, one block of model constants per set - qd_col_vars.h)
+    // (a constants table: the third form, one block of model constants per set and one control table - qd_col_vars.h)
+    case Family::F32:
+      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_f32_vars(a, adjoint, opts, st);
+      return a.nb_set ? launch_sweep_f32_sets(a, adjoint, opts, st) : launch_sweep_f32(a, adjoint, opts, st);
+    case Family::Slot:
+      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_lean64_vars(a, adjoint, opts, st);
+      return a.nb_set ? launch_sweep_lean64_sets(a, adjoint, opts, st) : launch_sweep_lean64(a, adjoint, opts, st);
     case Family::Col:
       if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_col_vars(a, adjoint, st);
       return a.nb_set ? launch_sweep_col_sets(a, adjoint, st) : launch_sweep_col(a, adjoint, st);

@@ -119,9 +119,12 @@ struct SweepPlan {
   }
   // Kernels that read one block of model constants per set exist for this plan (model-parameter ensemble on a standard-model handle):
   // the diagonal-split stationary iteration of the lean column family (k_*_col_vars), and under option ensemble_general the general
-  // family - Neumann and both direct Krylov forms (k_forward_vars / k_adjoint_vars)
+  // family - Neumann and both direct Krylov forms (k_forward_vars / k_adjoint_vars) -, under option ensemble_lean the lean slot and
+  // fp32-mixed families where the kernel's solver is a stationary iteration (k_forward_q32_vars / k_adjoint_q32_vars: a neumann request
+  // or a gmres request served by the Neumann stand-in; their Krylov kernels have no variants form)
   bool sweeps_vars(const TuneOpts& o) const {
-    return (family == Family::Col && cfg.gmres == 0 && neumann_split) || (family == Family::General && o.ensemble_general);
+    return (family == Family::Col && cfg.gmres == 0 && neumann_split) || (family == Family::General && o.ensemble_general) ||
+           (o.ensemble_lean && (family == Family::Slot || family == Family::F32) && cfg.gmres == 0);
   }
 };
 

@@ -176,6 +176,8 @@ struct TuneOpts {
   int batch_lean = 0;      // "batch_lean": the parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch) also shares launches on the lean slot,
                            // fp32-mixed and lean column families where their solver is a stationary iteration (0 = those go set by set, the default; 1 = one launch)
   int ensemble_general = 0;  // "ensemble_general": a model-parameter ensemble shares launches on the general kernel family too (k_forward_vars / k_adjoint_vars; 0 = variant by variant there)
+  int ensemble_lean = 0;   // "ensemble_lean": a model-parameter ensemble shares launches on the lean slot and fp32-mixed families too where their solver is a
+                           // stationary iteration (k_forward_q32_vars / k_adjoint_q32_vars; 0 = variant by variant there, the default)
   int ensemble_loop = 0;   // "ensemble_loop": a model-parameter ensemble (qd_optim_evalF_ensemble_model / qd_optim_evalGradF_ensemble_model) goes variant by
                            // variant even where the lean column kernels could share its launches (A/B switch; 0 = share, the default)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
@@ -278,6 +280,11 @@ hipError_t launch_sweep_lean64(const SweepArgs& a, bool adjoint, const TuneOpts&
 // elements per thread from ALL states of the launch, a.nb = sets x states per set (option lean64_sb pins it, as for the single sweep)
 hipError_t launch_sweep_f32_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_sweep_lean64_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+// ... with one block of model constants per set of a.nb_set states and ONE control table (qd_q32.hip compiled with -DQD_VARS=1:
+// k_forward_q32_vars / k_adjoint_q32_vars, the instantiations of the SETS launchers; the table of qd_col_vars.h in a.S.hcr): a Krylov
+// request or a missing table is an error.  Elements per thread of the uncoupled 2^5 system as in the SETS form, from a.nb = variants x states
+hipError_t launch_sweep_f32_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+hipError_t launch_sweep_lean64_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
 // lean column kernels (qd_col.hip): Lindblad Neumann sweeps of density matrices with 33..64 rows and runtime level counts
 bool collean_available(const DevSys& S, const TuneOpts& o);

@@ -1026,7 +1026,7 @@ struct EnsembleCall {
   double* grad_mean;                 // [ndesign] (gradient mode): sum_j w[j] grads[j]
   // variants of the standard model's constants instead (qd_optim_eval(Grad)F_ensemble_model; norms is null): the caller has uploaded
   // their blocks (qd_handle::variants_upload, vars_tab) - launches are shared on the third form of the lean column kernels and, with
-  // option ensemble_general, of the general kernels (SweepPlan::sweeps_vars)
+  // option ensemble_general, of the general kernels, with option ensemble_lean of the lean slot and fp32-mixed kernels (SweepPlan::sweeps_vars)
   bool model = false;
 };
 
@@ -1069,6 +1069,7 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
     // (grid.y of the per-set kernels; SweepArgs::ctl_set and gtab_set are 32 bits wide)
     // (a model-parameter ensemble: the diagonal-split stationary iteration of the lean column family - k_*_col_vars - whatever batch_lean says)
     // (... and, under option ensemble_general, the general family - k_forward_vars / k_adjoint_vars; never a dense handle: rejected by the caller)
+    // (... and, under option ensemble_lean, the stationary iterations of the lean slot and fp32-mixed families - k_*_q32_vars)
     const bool shares = ens && ens->model ? plan.sweeps_vars(h->opts) && !h->opts.ensemble_loop && !h->S.dense : plan.sweeps_sets(h->opts);
     bool concurrent = shares && plan.team == 1 && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
                       nset <= 65535 && h->batch_ctl_set() <= 0xffffffffull && h->batch_gtab_set() <= 0xffffffffull;
@@ -1268,7 +1269,8 @@ extern "C" int qd_optim_evalGradF_ensemble(qd_optim* o, const double* alpha, int
 // with the control vector replicated and k_*_col_vars / k_*_colj_vars reading variant j's constants from the table of qd_col_vars.h
 // (qd_handle::variants_upload; one plan from the largest row bounds among the variants).  With option ensemble_general = 1 they share
 // launches on the general family as well (one workgroup per state, Neumann and direct Krylov kernels alike): k_forward_vars /
-// k_adjoint_vars of qd_gen_vars.h.  Everything else - the other families,
+// k_adjoint_vars of qd_gen_vars.h; with option ensemble_lean = 1 on the lean slot and fp32-mixed families where the sweep's solver is a
+// stationary iteration: k_forward_q32_vars / k_adjoint_q32_vars of qd_q32.hip.  Everything else - the other families,
 // Krylov or plain-Neumann column plans, chunked shards, option ensemble_loop - goes variant by variant through the single evaluation
 // with the handle pointed at one variant after the other (qd_handle::point_at_variant).
 // ---------------------------------------------------------------------------------------------------------------

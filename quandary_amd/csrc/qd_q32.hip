@@ -31,10 +31,31 @@
 // set b / SweepArgs::nb_set (parameter-set batch, qd_optim_evalGradF_batch with option batch_lean), the addressing sweep_ctl<true>
 // gives the general kernels; everything else a workgroup touches is indexed by the state.  The kernel name and the table a sweep reads
 // are the only two places where the forms differ: without the define this file preprocesses to the text it had before they existed.
+//
+// With -DQD_VARS=1 (build/qd_q32_vars.o): the third form, k_forward_q32_vars / k_adjoint_q32_vars and their launchers - nothing else.
+// The states of a launch are a.nb / SweepArgs::nb_set sets as in the SETS form, a set is a variant of a model-parameter ensemble
+// (qd_optim_evalGradF_ensemble_model with option ensemble_lean) and every set reads the ONE control table.  The workgroup of state b takes
+// detune / xikl / J from the block of variant b / nb_set in the device table of qd_col_vars.h (it travels in S.hcr; wave-uniform address,
+// scalar loads) where Q32::init forms the diagonal of the Hamiltonian and keeps J_kl: the source of those constants (QD_Q32_CONSTS) and
+// the kernel name are the only places where this form differs.  g1 / g2 / g1off, level counts and hasJ remain the handle's; a variant
+// whose J of a pair is 0 keeps the coupled kernel with Jc = 0; selfkerr travels in the table and has no term on two levels.
 #ifndef QD_SETS
 #define QD_SETS 0
 #endif
-#if QD_SETS
+#ifndef QD_VARS
+#define QD_VARS 0
+#endif
+#if QD_SETS && QD_VARS
+#error "QD_SETS and QD_VARS are objects of their own"
+#endif
+#if QD_VARS
+#include "qd_col_vars.h"
+#define QD_Q32_FORWARD k_forward_q32_vars
+#define QD_Q32_ADJOINT k_adjoint_q32_vars
+#define QD_Q32_CTL(A) A.ctl
+#define QD_Q32_CONSTS(A, Q) \
+  ColVarConsts<Q> { col_vars_tab(A) + (size_t)((unsigned)blockIdx.x / (unsigned)A.nb_set) * col_vars_stride(Q, ColVarConsts<Q>::NP) }
+#elif QD_SETS
 #define QD_Q32_FORWARD k_forward_q32_sets
 #define QD_Q32_ADJOINT k_adjoint_q32_sets
 #define QD_Q32_CTL(A) (A.ctl + (size_t)((unsigned)blockIdx.x / (unsigned)A.nb_set) * A.ctl_set)
@@ -42,6 +63,10 @@
 #define QD_Q32_FORWARD k_forward_q32
 #define QD_Q32_ADJOINT k_adjoint_q32
 #define QD_Q32_CTL(A) A.ctl
+#endif
+#ifndef QD_Q32_CONSTS
+#define QD_Q32_CONSTS(A, Q) \
+  Q32SysConsts { A.S }
 #endif
 #define QD_Q32_STR2(x) #x
 #define QD_Q32_STR(x) QD_Q32_STR2(x)
@@ -73,6 +98,15 @@ __device__ __forceinline__ float rfma(float a, float b, float c) { return fmaf(a
 __device__ __forceinline__ double rfma(double a, double b, double c) { return fma(a, b, c); }
 __device__ __forceinline__ float uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 __device__ __forceinline__ double uniform(double v) { return to_scalar(v); }
+
+// Where Q32::init takes the constants a variant of a model-parameter ensemble may change: the kernel argument (this struct), or one
+// variant's block of the device table (ColVarConsts of qd_col_vars.h, the QD_VARS form)
+struct Q32SysConsts {
+  const DevSys& S;
+  __device__ __forceinline__ double detune(int k) const { return S.detune[k]; }
+  __device__ __forceinline__ double xikl(int p) const { return S.xikl[p]; }
+  __device__ __forceinline__ double J(int p) const { return S.J[p]; }
+};
 
 template <int Q, int SB, typename R = float, bool HJ = false>
 struct Q32 {
@@ -122,7 +156,8 @@ struct Q32 {
   R qb[Q], qk[Q];                // q_k with the sign of the bra / ket (k >= SB) digit of this thread [per step]
   R p[Q], q[Q];                  // controls of the current sub-step (wave-uniform)
 
-  __device__ __forceinline__ void init(const DevSys& S, bool = false) {
+  template <class C>
+  __device__ __forceinline__ void init(const DevSys& S, const C& K, bool = false) {
     const unsigned tid = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < EPT; j++) {
@@ -132,14 +167,14 @@ struct Q32 {
 #pragma unroll
       for (int k = 0; k < Q; k++) {
         const int a = (it >> brabit(k)) & 1, ap = (it >> ketbit(k)) & 1;
-        hd += S.detune[k] * a;  // the self-Kerr term a(a-1) vanishes for two levels
-        hdp += S.detune[k] * ap;
+        hd += K.detune(k) * a;  // the self-Kerr term a(a-1) vanishes for two levels
+        hdp += K.detune(k) * ap;
         d += S.g2[k] * (a * ap - 0.5 * (a + ap)) - S.g1[k] / 2.0 * (a + ap);
 #pragma unroll
         for (int l = k + 1; l < Q; l++) {
           const int b = (it >> brabit(l)) & 1, bp = (it >> ketbit(l)) & 1;
-          hd -= S.xikl[pair] * a * b;
-          hdp -= S.xikl[pair] * ap * bp;
+          hd -= K.xikl(pair) * a * b;
+          hdp -= K.xikl(pair) * ap * bp;
           pair++;
         }
       }
@@ -172,7 +207,7 @@ struct Q32 {
           const unsigned bm = (1u << brabit(k)) | (1u << brabit(l)), km = (1u << ketbit(k)) | (1u << ketbit(l));
           ajb[pair] = (tid ^ bm) << ESH;
           ajk[pair] = (tid ^ km) << ESH;
-          Jc[pair] = uniform((R)S.J[pair]);
+          Jc[pair] = uniform((R)K.J(pair));
           pjs[pair] = pjc[pair] = qjs[pair] = qjc[pair] = (R)0;
         }
     }
@@ -205,7 +240,7 @@ struct Q32 {
               jak[pr][j] = (unsigned)slotbit(j, k) != bp ? (tid ^ (1u << ketbit(l))) << ESH : ZOFF;
             }
           }
-          Jc[pr] = uniform((R)S.J[pr]);
+          Jc[pr] = uniform((R)K.J(pr));
           jc[pr] = js[pr] = (R)0;
         }
     }
@@ -493,7 +528,8 @@ struct Q32<Q, SB, float, false> {
     return v;
   }
 
-  __device__ __forceinline__ void init(const DevSys& S, bool trans = false) {
+  template <class C>
+  __device__ __forceinline__ void init(const DevSys& S, const C& K, bool trans = false) {
     const unsigned tid = threadIdx.x;
 #pragma unroll
     for (int j = 0; j < EPT; j++) {
@@ -503,14 +539,14 @@ struct Q32<Q, SB, float, false> {
 #pragma unroll
       for (int k = 0; k < Q; k++) {
         const int a = (it >> brabit(k)) & 1, ap = (it >> ketbit(k)) & 1;
-        hd += S.detune[k] * a;
-        hdp += S.detune[k] * ap;
+        hd += K.detune(k) * a;
+        hdp += K.detune(k) * ap;
         d += S.g2[k] * (a * ap - 0.5 * (a + ap)) - S.g1[k] / 2.0 * (a + ap);
 #pragma unroll
         for (int l = k + 1; l < Q; l++) {
           const int b = (it >> brabit(l)) & 1, bp = (it >> ketbit(l)) & 1;
-          hd -= S.xikl[pair] * a * b;
-          hdp -= S.xikl[pair] * ap * bp;
+          hd -= K.xikl(pair) * a * b;
+          hdp -= K.xikl(pair) * ap * bp;
           pair++;
         }
       }
@@ -641,7 +677,8 @@ struct Team32 {
   int cur, redslot;
   static constexpr bool PARK = EPT > 1;
 
-  __device__ __forceinline__ void init(const DevSys& S, unsigned char* smem, bool trans = false) {
+  template <class C>
+  __device__ __forceinline__ void init(const DevSys& S, const C& K, unsigned char* smem, bool trans = false) {
     buf = reinterpret_cast<f2*>(smem);
     red = reinterpret_cast<double*>(smem + 2 * sizeof(f2) * DIM + ZPAD);
     acc = reinterpret_cast<double2*>(smem + acc_off());
@@ -651,7 +688,7 @@ struct Team32 {
     if constexpr (ST::JS1) {  // the zero elements (see Q32): at 2 D and 3 D for slot 0, half a vector further for slot 1 (D = bytes of a vector)
       if (threadIdx.x < 4) *reinterpret_cast<f2*>(smem + (4 + threadIdx.x) * (sizeof(f2) * DIM / 2)) = f2{0, 0};
     }
-    st.init(S, trans);  // (the packed fp32 stencil keeps the T1 coefficients of one direction only)
+    st.init(S, K, trans);  // (the packed fp32 stencil keeps the T1 coefficients of one direction only)
   }
   // coupled 2^5 kernels: zero elements at 2 D, 2.5 D, 3 D, 3.5 D behind the two vectors; the reduction scratch sits between the first two,
   // the parked accumulators behind the last
@@ -1178,7 +1215,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
   constexpr int EPT = TM::EPT, DIM = TM::DIM;
   const DevSys& S = A.S;
   TM tm;
-  tm.init(S, smem);
+  tm.init(S, QD_Q32_CONSTS(A, Q), smem);
   const int ic = blockIdx.x;
   double2 x[EPT];  // the state itself: fp64 accumulators
   {
@@ -1273,7 +1310,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
   constexpr int EPT = TM::EPT, DIM = TM::DIM;
   const DevSys& S = A.S;
   TM tm;
-  tm.init(S, smem, true);
+  tm.init(S, QD_Q32_CONSTS(A, Q), smem, true);
   const int ic = blockIdx.x;
   double2 xb[EPT];  // the adjoint state: fp64 accumulators
   {
@@ -1356,7 +1393,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
   }
 }
 
-#if !QD_SETS
+#if !QD_SETS && !QD_VARS
 // single operator application (test hook: qd_apply_rhs with QD_PRECISION_F32MIXED; timing loop of the MFMA measurement)
 template <int Q, int SB, typename R, bool HJ = false>
 __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (Q32<Q, SB, R>::MINW >> (HJ ? 1 : 0))) k_apply_q32(const DevSys S, const double* __restrict__ ctlrow, int transpose,
@@ -1366,7 +1403,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (Q32<Q, SB, R>::MINW >> (
   typedef typename TM::f2 f2;
   constexpr int EPT = TM::EPT, DIM = TM::DIM;
   TM tm;
-  tm.init(S, smem, transpose != 0);
+  tm.init(S, Q32SysConsts{S}, smem, transpose != 0);
   const int ic = blockIdx.x;
   f2 x[EPT], y[EPT];
   const double* x0 = xin + (size_t)ic * 2 * DIM;
@@ -1507,7 +1544,7 @@ __global__ void __launch_bounds__(64) k_apply_mfma32(const DevSys S, const doubl
   }
 }
 
-#endif  // !QD_SETS
+#endif  // !QD_SETS && !QD_VARS
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -1530,7 +1567,7 @@ static hipError_t go_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
   return hipGetLastError();
 }
-#if !QD_SETS
+#if !QD_SETS && !QD_VARS
 template <int Q, int SB, typename R, bool HJ = false>
 static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const double* x, double* y, int nb, int nrep, hipStream_t st) {
   constexpr int nt = Q32<Q, SB, R>::NT;
@@ -1550,13 +1587,41 @@ static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const do
 // 5.5 -> 5.3).  Larger batches keep two 256-thread groups per CU, four elements per thread; so do the Krylov kernels (the only form built).
 // A sets launch (parameter-set batch) counts every state of the launch, a.nb = sets x states of one set, because that is what fills the
 // chip: a batch may run <5, 2, ...> where the single evaluation of the same shard runs <5, 1, ...>.  The option lean64_sb pins it for both.
+// A variants launch (model-parameter ensemble, option ensemble_lean) counts the same way, a.nb = variants x states of one variant: an
+// uncoupled 2^5 ensemble may run <5, 2, ...> where one variant alone - the loop, a fresh handle - runs <5, 1, ...>; lean64_sb pins that too.
 static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
   if (a.use_gmres) return 2;
   if (o.lean64_sb == 1 || o.lean64_sb == 2) return o.lean64_sb;
   return a.nb <= 256 ? 1 : 2;
 }
 
-#if QD_SETS
+#if QD_VARS
+// The sweeps of a model-parameter ensemble: a.nb states = a.nb / a.nb_set variants, one control table, the constants table in a.S.hcr.
+// The instantiations are those of the SETS launchers below, picked by the same rules; no Krylov form is built: a request for one, a
+// dense handle or a missing table is an error, never another kernel.
+static bool vars_args_ok(const SweepArgs& a) {
+  return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0 && !a.S.dense && col_vars_tab(a) != nullptr && a.S.npairs == a.S.Q * (a.S.Q - 1) / 2;
+}
+hipError_t launch_sweep_f32_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  if (!vars_args_ok(a)) return hipErrorInvalidValue;
+  if (a.S.hasJ) {
+    if (a.S.Q == 5) return go_sweep<5, 1, float, false, true>(a, adjoint, st);
+    if (a.S.Q == 4) return go_sweep<4, 0, float, false, true>(a, adjoint, st);
+    return hipErrorInvalidValue;
+  }
+  if (a.S.Q == 5) return lean64_sb(a, o) == 1 ? go_sweep<5, 1, float>(a, adjoint, st) : go_sweep<5, 2, float>(a, adjoint, st);
+  if (a.S.Q == 4) return go_sweep<4, 0, float>(a, adjoint, st);
+  if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);
+  return hipErrorInvalidValue;
+}
+hipError_t launch_sweep_lean64_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  if (!vars_args_ok(a) || (a.S.Q != 4 && a.S.Q != 5)) return hipErrorInvalidValue;
+  if (a.S.Q == 4 && a.S.hasJ) return go_sweep<4, 0, double, false, true>(a, adjoint, st);
+  if (a.S.Q == 5 && a.S.hasJ) return go_sweep<5, 1, double, false, true>(a, adjoint, st);
+  if (a.S.Q == 4) return go_sweep<4, 0, double>(a, adjoint, st);
+  return lean64_sb(a, o) == 1 ? go_sweep<5, 1, double>(a, adjoint, st) : go_sweep<5, 2, double>(a, adjoint, st);
+}
+#elif QD_SETS
 // The sweeps of a parameter-set batch: a.nb states = a.nb / a.nb_set sets, each reading its own control table.  The instantiations are
 // those the launchers below pick for a stationary iteration; the Krylov kernels have no SETS form (their degree tuner keeps statistics
 // per handle that a launch of mixed sets would blur): a request for one is an error, never another kernel.
@@ -1642,6 +1707,6 @@ hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transp
   if (S.Q == 4) return go_app<4, 0, double>(S, ctlrow, transpose, x, y, nb, 1, st);
   return go_app<5, 2, double>(S, ctlrow, transpose, x, y, nb, 1, st);
 }
-#endif  // QD_SETS
+#endif  // QD_VARS, QD_SETS
 
 }  // namespace qd
