@@ -448,6 +448,31 @@ int qd_optim_evalGradF_ensemble_model(qd_optim* o, const double* alpha, int nvar
                                       const double* crosskerr, const double* Jkl, const double* weights, qd_objective_value* vals,
                                       qd_objective_value* mean, double* grads, double* grad_mean);
 
+/* Objective, gradient and the derivatives of the objective with respect to the constants of the STANDARD Hamiltonian model, from ONE
+ * forward and ONE adjoint sweep.  val and grad are those of qd_optim_evalGradF(alpha).  d_transfreq [nosc], d_selfkerr [nosc] and
+ * d_crosskerr [npairs, in the pair order of qd_system] receive d objective / d constant per GHz of the qd_system field; any of the
+ * three may be NULL.  The function differentiated is the one qd_optim_evalF_ensemble_model samples: a constant is moved as on a handle
+ * created from the same qd_system with that one entry changed, while rotation frequencies (the frame and the control table), level
+ * counts, T1/T2, Jkl, controls, target and penalties are held fixed; the Tikhonov and control-variation terms do not depend on the
+ * constants.  The derivative is the discrete one of the implicit-midpoint family, exact to the tolerance of the linear solver like the
+ * control gradient: with the h-scaled adjoint stage kbar_s and the stored primal stage z_s of sub-step s,
+ *   d objective / d theta = sum over the initial conditions and sub-steps of kbar_s^T (dM / d theta) z_s,
+ * where dM / d theta is diagonal and time-independent: for the element with bra digits i_k and ket digits i'_k (Schroedinger: no ket
+ * digits) w = kbar.x z.y - kbar.y z.x times 2 pi (i_k - i'_k) for transfreq[k], - pi (i_k (i_k - 1) - i'_k (i'_k - 1)) for selfkerr[k]
+ * and - 2 pi (i_k i_l - i'_k i'_l) for crosskerr[kl].  kbar is never stored, so the sums are formed inside the adjoint kernel: the call
+ * plans BOTH sweeps on the general kernel family (one workgroup per state in LDS, as options no_collean / no_lean64 would - systems that
+ * otherwise run on a lean family included), the forward sweep on k_forward, the adjoint sweep on its sensitivity form k_adjoint_sens
+ * (qd_last_kernel).  The handle's options, solver latch and tuner state are restored afterwards: the next qd_optim_evalGradF returns
+ * what it returned before, on the kernels it ran on before.
+ * Errors: a null o, alpha, val or grad: QD_ERR_INVALID; a user-Hamiltonian handle or an objective created with nranks > 1:
+ * QD_ERR_STATE; explicit Euler, QD_PRECISION_F32MIXED, a state beyond one CU's LDS (the global-memory kernels, dim > 4096), a shard
+ * whose stored trajectory would need chunking, and whatever qd_optim_evalGradF rejects: QD_ERR_UNSUPPORTED, the message naming the
+ * reason; no sweep is launched for any of them.
+ * Not built: d / d Jkl (off-diagonal), d / d T1, T2, sensitivity forms of the lean slot and lean column kernels, sensitivities of an
+ * ensemble mean, several ranks. */
+int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_objective_value* val, double* grad, double* d_transfreq,
+                             double* d_selfkerr, double* d_crosskerr);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, initial conditions sharded over the ranks.
  * Replaces the reference's comm_init communicator (src/main.cpp:133-177) and its

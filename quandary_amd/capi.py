@@ -181,7 +181,7 @@ EXPORTS = [
     "qd_comm_allreduce", "qd_comm_barrier", "qd_optim_evalF_dist", "qd_optim_evalGradF_dist", "qd_optim_last_chunks", "qd_set_precision", "qd_get_precision", "qd_bench_apply_f32", "qd_get_observables", "qd_set_option",
     "qd_optim_evalF_batch", "qd_optim_evalGradF_batch", "qd_optim_last_batch_sets",
     "qd_optim_evalF_ensemble", "qd_optim_evalGradF_ensemble",
-    "qd_optim_evalF_ensemble_model", "qd_optim_evalGradF_ensemble_model",
+    "qd_optim_evalF_ensemble_model", "qd_optim_evalGradF_ensemble_model", "qd_optim_evalGradF_model",
 ]
 COMM_ID_BYTES = 128
 PRECISION = {"f64": 0, "f32mixed": 1}
@@ -259,6 +259,7 @@ def load_library(path=None):
                                                   C.POINTER(qd_objective_value)]
     lib.qd_optim_evalGradF_ensemble_model.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value),
                                                       C.POINTER(qd_objective_value), c_dp, c_dp]
+    lib.qd_optim_evalGradF_model.argtypes = [vp, c_dp, C.POINTER(qd_objective_value), c_dp, c_dp, c_dp, c_dp]
     lib.qd_comm_unique_id.argtypes = [c_u8p]
     lib.qd_comm_create.argtypes = [c_u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.qd_comm_create_from_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp)]
@@ -674,6 +675,25 @@ class Optim:
                "qd_optim_evalGradF_ensemble_model")
         return (mean.as_dict(), gm[:nd], [vals[j].as_dict() for j in range(nvar)],
                 np.ascontiguousarray(g[:nvar, :nd]) if per_variant else None)
+
+    def evalGradF_model(self, alpha, want=("transfreq", "selfkerr", "crosskerr")):
+        """qd_optim_evalGradF_model: (dict, grad, {"transfreq": [nosc], "selfkerr": [nosc], "crosskerr": [npairs]}) - the objective and
+        gradient of evalGradF(alpha) and d objective / d constant of the standard model per GHz of the system's field, pairs in the
+        system's order, from one forward and one adjoint sweep (k_forward / k_adjoint_sens on the general kernel family).  The function
+        differentiated is the one evalF_ensemble_model samples.  A name missing from `want` is passed as NULL and comes back as None."""
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        val = qd_objective_value()
+        g = np.zeros(max(self.h.ndesign, 1))
+        nosc = self.h.spec.system.nosc
+        npairs = nosc * (nosc - 1) // 2
+        out = {"transfreq": np.zeros(nosc) if "transfreq" in want else None,
+               "selfkerr": np.zeros(nosc) if "selfkerr" in want else None,
+               "crosskerr": np.zeros(max(npairs, 1)) if "crosskerr" in want else None}
+        _check(self.lib, self.lib.qd_optim_evalGradF_model(self._o, dptr(alpha), C.byref(val), dptr(g), dptr(out["transfreq"]),
+                                                           dptr(out["selfkerr"]), dptr(out["crosskerr"])), "qd_optim_evalGradF_model")
+        if out["crosskerr"] is not None:
+            out["crosskerr"] = out["crosskerr"][:npairs]
+        return val.as_dict(), g[: self.h.ndesign], out
 
     # multi-GPU: every rank calls with the RCCL communicator (qd_comm*) created for the same rank / nranks
     def evalF_dist(self, comm, alpha):

@@ -1,6 +1,7 @@
 // qd_adjoint_body.h - the body of the adjoint sweep kernels of qd_device.h, included inside k_adjoint and k_adjoint_vars (see
-// qd_forward_body.h).  In scope where it is included: the template arguments Q, LIND, VAR, QUBIT, GM, PLAIN, the constants SETS and
-// VARS, the kernel argument `const SweepArgs A`.
+// qd_forward_body.h) and k_adjoint_sens.  In scope where it is included: the template arguments Q, LIND, VAR, QUBIT, GM, PLAIN, the
+// constants SETS, VARS and SENS (the sensitivity form, qd_sens.h: false in k_adjoint and k_adjoint_vars, whose code is that of the body
+// without it), the kernel argument `const SweepArgs A`.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef Team<Q, LIND, VAR, QUBIT, GM, VARS> TM;
   constexpr int EPT = TM::EPT;
@@ -92,6 +93,16 @@
   if (ZAHEAD && !ee && A.nsub > 0) {
     load_stage(A.nsub - 1, znext);
     load_step<Q>(sweep_ctl<SETS>(A, tm.ic0) + (size_t)(A.nsub - 1) * A.cs, cn, jpairs);
+  }
+  // sensitivity form: packed level digits of the thread's elements (from their natural index), the NS sums of the whole sweep
+  constexpr int NSENS = SENS ? sens_count(Q) : 1;
+  double sacc[NSENS];
+  unsigned sbra[SENS ? EPT : 1], sket[SENS ? EPT : 1];
+  if constexpr (SENS) {
+#pragma unroll
+    for (int i = 0; i < NSENS; i++) sacc[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < EPT; j++) sens_decode<Q, LIND>(S, at_use<EPT>(tm.st.it[j]), sbra[j], sket[j]);
   }
 
   vm_drain();
@@ -275,6 +286,11 @@
             }
           }
       }
+      if constexpr (SENS) {  // kbar^T (dM/d theta) z of the diagonal, time-independent model operators (qd_sens.h)
+#pragma unroll
+        for (int j = 0; j < EPT; j++)
+          sens_add<Q, LIND>(sbra[j], sket[j], tm.ok(j) ? kb[j].x * z[j].y - kb[j].y * z[j].x : 0.0, sacc);
+      }
       store_coeffs();
       // xbar += M^T kbar
       tm.publish(kb);
@@ -292,6 +308,7 @@
       for (int j = 0; j < EPT; j++) xn[j] = x[j];
     }
   }
+  if constexpr (SENS) sens_store<NSENS>(tm, sacc, A.S.tred + (size_t)tm.ic0 * NSENS);  // [nb][NS], summed over the states on the host side
   if (A.xbar0) {
 #pragma unroll
     for (int j = 0; j < EPT; j++)

@@ -2613,6 +2613,8 @@ struct Team {
   }
 };
 
+#include "qd_sens.h"  // the helpers of the sensitivity form of the adjoint sweep (k_adjoint_sens below)
+
 // ---------------------------------------------------------------------------------------------
 // forward sweep: TimeStepper::solveODE for every initial condition of the batch
 // ---------------------------------------------------------------------------------------------
@@ -2681,12 +2683,21 @@ __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_forward_vars(const Sweep
 // ---------------------------------------------------------------------------------------------
 template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false, bool SETS = false>
 __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint(const SweepArgs A) {
-  constexpr bool VARS = false;
+  constexpr bool VARS = false, SENS = false;
 #include "qd_adjoint_body.h"
 }
 template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false>
 __global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint_vars(const SweepArgs A) {
-  constexpr bool SETS = false, VARS = true;
+  constexpr bool SETS = false, VARS = true, SENS = false;
+#include "qd_adjoint_body.h"
+}
+// the sensitivity form (qd_sens.h; qd_optim_evalGradF_model): the adjoint sweep of a single evaluation that also sums kbar^T (dM/d theta) z
+// over its sub-steps for the diagonal model constants theta - detunings, self-Kerr and cross-Kerr coefficients - into
+// SweepArgs::S.tred [nb][sens_count(Q)] (the partial-sum buffer of the global-memory kernels, which this form has no instantiation of:
+// the layout of the kernel argument stays that of every other sweep kernel).  Reads what k_forward stored; the standard model only.
+template <int Q, bool LIND, int VAR, bool QUBIT, bool GM, bool PLAIN = false>
+__global__ void __launch_bounds__(Variant<VAR>::MAXB) k_adjoint_sens(const SweepArgs A) {
+  constexpr bool SETS = false, VARS = false, SENS = true;
 #include "qd_adjoint_body.h"
 }
 

@@ -71,7 +71,7 @@ extern "C" void qd_destroy(qd_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
-  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0, &h->d_vconst, &h->d_pencarry}) b->release();
+  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0, &h->d_vconst, &h->d_pencarry, &h->d_sens, &h->d_senssum}) b->release();
   h->h_bparams.release();
   h->h_betable.release();
   h->h_bgrad.release();
@@ -1500,12 +1500,21 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   a.xbarT = dxbarT;
   a.jbar = djbar;
   a.coeff = d_coeff.p;
+  const int nsens = sens_columns(S.Q);
+  if (sens) {  // the sensitivity form of the general family's adjoint sweep: never another kernel in its place
+    if (plan.family != Family::General || sets || S.dense || sol.stepper == QD_STEPPER_EE || !a.ztraj)
+      return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state sweeps them (standard model, implicit-midpoint family, one control vector)");
+    if ((r = d_sens.ensure((size_t)nb * nsens)) || (r = d_senssum.ensure(nsens))) return r;
+    a.S.tred = d_sens.p;
+  }
   QD_HIP(hipEventRecord(ev2, stream));
   take_kernel(1);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 1))) return r;
-  QD_HIP(launch_sweep(a, plan, true, opts, stream));
+  if (sens) QD_HIP(launch_adjoint_sens(a, plan.cfg, stream));
+  else QD_HIP(launch_sweep(a, plan, true, opts, stream));
   last_kernel[1] = take_kernel(1);
   QD_HIP(hipEventRecord(ev3, stream));
+  if (sens) QD_HIP(launch_reduce_coeff(d_sens.p, nb, nsens, d_senssum.p, accumulate ? 1 : 0, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_adj = a.sched != nullptr;
   if (sets) QD_HIP(launch_reduce_coeff_sets(d_coeff.p, nb / sets, (int)ncol, d_coeffsum.p, sets, stream));  // once per set, over its own states

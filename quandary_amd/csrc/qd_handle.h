@@ -304,6 +304,12 @@ struct qd_handle {
   const double* vars_tab = nullptr;
   qd::RowBound vars_bound{};
   int variants_upload(int nvar, const double* blocks, const double* alpha);  // d_vconst, vars_host and vars_bound (at the control vector alpha)
+  // Model-constant sensitivities (qd_optim_evalGradF_model): while sens is set the adjoint sweep runs on the sensitivity form of the
+  // general family (k_adjoint_sens, qd_sens.h) - any other plan is an error - and leaves the sums over the states of
+  // kbar^T (dM/d theta) z in d_senssum [2 Q + npairs]: detunings, self-Kerr, cross-Kerr coefficients, in rad/ns and without the factors
+  // -1/2 and -1 of the Kerr terms (the caller applies them with the unit).  d_sens: the per-state sums the kernel stores.
+  bool sens = false;
+  qd::DBuf d_sens, d_senssum;
   size_t batch_ctl_set() const { return sched_t.size() * (size_t)cs; }    // rows the step table really has x cs
   size_t batch_etable_set() const { return etimes.size() * (size_t)cs; }
   const double* batch_table() const { return d_btable.p + (size_t)batch_first * batch_ctl_set(); }

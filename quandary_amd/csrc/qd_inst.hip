@@ -9,6 +9,8 @@
 // With -DQD_VARS=1 (build/qd_vars_*.o): the third form, k_forward_vars / k_adjoint_vars - one block of model constants per set of
 // SweepArgs::nb_set states and one control table for all (model-parameter ensemble, qd_optim_evalGradF_ensemble_model; qd_gen_vars.h) -
 // for the same LDS variants of the standard Hamiltonian model only (QD_B = 0 | 1): no dense variants, no variant 16.
+// With -DQD_SENS=1 (build/qd_sens_*.o): the sensitivity form of the adjoint sweep, k_adjoint_sens (qd_sens.h; qd_optim_evalGradF_model) -
+// the adjoint roles only (QD_PART = 1 | 3; the forward sweep is k_forward itself), for the instantiations k_adjoint_vars has.
 #include "qd_device.h"
 #include "qd_big.h"
 #ifndef QD_VARS
@@ -19,6 +21,12 @@
 #if QD_B == 2 || defined(QD_SETS)
 #error "QD_VARS: the standard Hamiltonian model only (QD_B = 0 | 1), and not together with QD_SETS"
 #endif
+#endif
+#ifndef QD_SENS
+#define QD_SENS 0
+#endif
+#if QD_SENS && (QD_B == 2 || defined(QD_SETS) || QD_VARS || (QD_PART != 1 && QD_PART != 3))
+#error "QD_SENS: the adjoint roles (QD_PART = 1 | 3) of the standard Hamiltonian model only (QD_B = 0 | 1), and not together with QD_SETS or QD_VARS"
 #endif
 
 #if !defined(QD_Q) || !defined(QD_L) || !defined(QD_B) || !defined(QD_PART)
@@ -32,6 +40,7 @@ constexpr bool kGmPart = (QD_PART >= 2);
 #endif
 constexpr bool kSets = (QD_SETS != 0);
 constexpr bool kVars = (QD_VARS != 0);
+[[maybe_unused]] constexpr bool kSens = (QD_SENS != 0);  // (read by the adjoint roles only)
 
 namespace qd {
 
@@ -122,7 +131,7 @@ static hipError_t go_apply(const DevSys& S, const double* ctlrow, int transpose,
 #if QD_PART == 1 || QD_PART == 3
 template <int VAR>
 static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if constexpr (VAR == 16 && !kSets && !kVars && variant_built(QD_Q, kLind, QD_B, VAR)) {
+  if constexpr (VAR == 16 && !kSets && !kVars && !kSens && variant_built(QD_Q, kLind, QD_B, VAR)) {
     if constexpr (!kGmPart) {
       if (a.stepper_ee) {
         note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, false, true);
@@ -142,6 +151,19 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     hipError_t e = set_lds(kf, cfg.lds);
     if (e != hipSuccess) return e;
     note_kernel(1, "k_adjoint_vars", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
+    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
+    return hipGetLastError();
+#elif QD_SENS
+  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
+    auto kf = k_adjoint_sens<QD_Q, kLind, VAR, kQubit, kGmPart, false>;
+    bool plain = false;
+    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
+      plain = plain_sweep(a, cfg, 1);
+      if (plain) kf = k_adjoint_sens<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
+    }
+    hipError_t e = set_lds(kf, cfg.lds);
+    if (e != hipSuccess) return e;
+    note_kernel(1, "k_adjoint_sens", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
     hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
     return hipGetLastError();
 #else
@@ -187,6 +209,9 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
 #define QD_FWDGM inst_forwardgmvars_
 #define QD_ADJ inst_adjointvars_
 #define QD_ADJGM inst_adjointgmvars_
+#elif QD_SENS
+#define QD_ADJ inst_adjointsens_
+#define QD_ADJGM inst_adjointgmsens_
 #elif QD_SETS
 #define QD_FWD inst_forwardsets_
 #define QD_FWDGM inst_forwardgmsets_

@@ -239,6 +239,12 @@ hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStre
 // qd_col_vars.h in a.S.hcr, qd_gen_vars.h): the LDS variants of the standard Hamiltonian model, Neumann and GMRES kernels
 hipError_t launch_forward_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 hipError_t launch_adjoint_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+// the sensitivity form of the adjoint sweep of a single evaluation (qd_inst.hip with -DQD_SENS=1: k_adjoint_sens, the template arguments
+// of the kernel launch_adjoint picks for the same arguments; qd_sens.h): besides the gradient coefficients the per-state sums
+// kbar^T (dM/d theta) z over all sub-steps for the detunings, self-Kerr and cross-Kerr coefficients, [nb][2 Q + npairs] into a.S.tred.
+// The LDS variants of the standard Hamiltonian model, implicit-midpoint family; anything else is an error
+hipError_t launch_adjoint_sens(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+inline int sens_columns(int Q) { return 2 * Q + Q * (Q - 1) / 2; }
 // control tables of nset parameter vectors in one launch: params [nset][ndesign] -> table [nset][nrows][cs], table2 [nset][nrows2][cs]
 hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int ndesign, int nset, const double* times, const double* hs, int nrows,
                                 double* table, const double* times2, const double* hs2, int nrows2, double* table2, int cs,

@@ -798,6 +798,23 @@ hipError_t launch_adjoint_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStre
   return adj_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
 }
 
+// the sensitivity form of the adjoint sweep (qd_inst.hip with -DQD_SENS=1: k_adjoint_sens, qd_sens.h), index [qubit][lindblad][Q-1]: the
+// standard Hamiltonian model on the LDS variants, an implicit-midpoint stepper, one control table, the per-state sums into a.S.tred
+#define QD_DECLN(q, l, b) hipError_t inst_adjointsens_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
+#define QD_DECLN_Q(l, b) QD_DECLN(1, l, b) QD_DECLN(2, l, b) QD_DECLN(3, l, b) QD_DECLN(4, l, b) QD_DECLN(5, l, b)
+QD_DECLN_Q(0, 0) QD_DECLN_Q(1, 0) QD_DECLN_Q(0, 1) QD_DECLN_Q(1, 1)
+QD_DECLN(6, 0, 0) QD_DECLN(7, 0, 0) QD_DECLN(8, 0, 0) QD_DECLN(6, 0, 1) QD_DECLN(7, 0, 1) QD_DECLN(8, 0, 1)
+QD_DECLN(6, 1, 0) QD_DECLN(7, 1, 0) QD_DECLN(8, 1, 0)
+static const sweep_fn adj_sens_tab[2][2][8] = {{QD_ROW8(inst_adjointsens_, 0, 0), QD_ROW8(inst_adjointsens_, 1, 0)},
+                                               {QD_ROW8(inst_adjointsens_, 0, 1), QD_ROW(inst_adjointsens_, 1, 1)}};
+// a dense handle, variant 16, explicit Euler, a set axis, a missing output buffer or a missing instantiation is an error
+hipError_t launch_adjoint_sens(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if (a.S.Q < 1 || a.S.Q > 8 || (cfg.qubit != 0 && cfg.qubit != 1) || cfg.var == 16 || a.nb_set != 0 || a.S.dense || a.stepper_ee || !a.S.tred ||
+      !a.ztraj || a.S.npairs != a.S.Q * (a.S.Q - 1) / 2 || !adj_sens_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
+    return hipErrorInvalidValue;
+  return adj_sens_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+}
+
 hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   if (a.S.Q < 1 || a.S.Q > 8 || !fwd_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
   return fwd_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);

@@ -1356,3 +1356,83 @@ extern "C" int qd_optim_evalGradF_ensemble_model(qd_optim* o, const double* alph
 }
 
 extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_batch_sets : QD_ERR_INVALID; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Model-constant sensitivities: the objective, its gradient and d objective / d (transfreq, selfkerr, crosskerr) from one forward and
+// one adjoint sweep.  The operators dM/d theta of these constants are diagonal and time-independent, so kbar^T (dM/d theta) z costs
+// one multiply-add per element and constant where the adjoint kernel forms the control-gradient coefficients from the same kbar and z
+// (qd_sens.h); kbar is never stored, so the sums cannot be formed anywhere else.  Only the general family has that kernel
+// (k_adjoint_sens): both sweeps are planned there, as options no_collean / no_lean64 would, and the handle is put back afterwards.
+// ---------------------------------------------------------------------------------------------------------------
+// leaves the handle on its own options, plan latch and tuner state however the call ends
+struct SensScope {
+  qd_handle* h;
+  int no_collean, no_lean64, latch, poly[7];
+  bool frozen;
+  explicit SensScope(qd_handle* hh)
+      : h(hh), no_collean(hh->opts.no_collean), no_lean64(hh->opts.no_lean64), latch(hh->sub_latch),
+        poly{hh->poly_cur, hh->poly_lo, hh->poly_hi, hh->last_poly, hh->poly_steps, hh->fwd_poly, hh->poly_slow}, frozen(hh->poly_frozen) {
+    h->opts.no_collean = h->opts.no_lean64 = 1;
+    h->sub_latch = -1;  // (the gates decide for the forced family, as on a fresh handle with those options)
+    h->sens = true;
+  }
+  ~SensScope() {
+    h->sens = false;
+    h->opts.no_collean = no_collean;
+    h->opts.no_lean64 = no_lean64;
+    h->sub_latch = latch;  // (the stand-in gates of the handle's own plan: not what the forced family decided)
+    h->poly_cur = poly[0], h->poly_lo = poly[1], h->poly_hi = poly[2], h->last_poly = poly[3], h->poly_steps = poly[4], h->fwd_poly = poly[5],
+    h->poly_slow = poly[6], h->poly_frozen = frozen;
+    h->params_dirty = true;
+    h->traj_valid = false;  // (the stored stages have the general family's layout)
+  }
+};
+
+extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_objective_value* val, double* grad, double* d_transfreq,
+                                        double* d_selfkerr, double* d_crosskerr) {
+  const std::string who = "qd_optim_evalGradF_model";
+  if (!o || !alpha || !val || !grad) return fail(QD_ERR_INVALID, who + ": null argument");
+  if (o->nranks != 1) return fail(QD_ERR_STATE, who + ": single-rank entry point");
+  qd_handle* h = o->h;
+  if (h->S.dense) return fail(QD_ERR_STATE, who + ": a user-Hamiltonian handle has no model constants");
+  if (h->sol.stepper == QD_STEPPER_EE)
+    return fail(QD_ERR_UNSUPPORTED, who + ": explicit Euler - the sensitivity form of the adjoint sweep is built for the implicit-midpoint family only");
+  if (h->precision == QD_PRECISION_F32MIXED)
+    return fail(QD_ERR_UNSUPPORTED, who + ": fp32-mixed precision - the sensitivity form of the adjoint sweep is an fp64 kernel of the general family");
+  if (h->has_pipulse || h->has_ampbasis)
+    return fail(QD_ERR_UNSUPPORTED, who + ": pi-pulses and the spline_amplitude parameterisation have no gradient (qd_optim_evalGradF)");
+  QD_HIP(qd::use_device(h->device));
+  const int Q = h->S.Q, np = h->S.npairs, nl = o->nlocal, ns = sens_columns(Q);
+  int r;
+  std::vector<double> s(ns);
+  {
+    SensScope scope(h);
+    if ((r = qd_set_params(h, alpha, h->ndesign))) return r;
+    {
+      PenaltyScope ps(h, o->pen);
+      StagesScope ss(h);
+      const SweepPlan plan = h->plan_sweep(nl, false);
+      if (plan.family == Family::Global)
+        return fail(QD_ERR_UNSUPPORTED, who + ": the state does not fit one CU's LDS (dim > 4096) - the global-memory kernels have no sensitivity form");
+      if (plan.family != Family::General)
+        return fail(QD_ERR_UNSUPPORTED, who + ": the sweep is not planned on the general kernel family, the only one with a sensitivity form");
+      if (!trajectory_fits(h, nl, &o->tg))
+        return fail(QD_ERR_UNSUPPORTED, who + ": the stored trajectory of the shard does not fit device memory and would be swept in chunks - not built for the sensitivity form");
+    }
+    if ((r = qd_optim_evalGradF(o, alpha, val, grad))) return r;
+    if (o->last_chunks != 1) return fail(QD_ERR_UNSUPPORTED, who + ": the shard was swept in chunks - not built for the sensitivity form");
+    QD_HIP(hipMemcpyAsync(s.data(), h->d_senssum.p, sizeof(double) * ns, hipMemcpyDeviceToHost, h->stream));
+    QD_HIP(hipStreamSynchronize(h->stream));
+    o->stored = false;
+    o->forward_done = false;
+  }
+  // per GHz of the qd_system fields: detune = 2 pi (transfreq - rotfreq), xi = 2 pi selfkerr, xikl = 2 pi crosskerr (model_detune,
+  // model_kerr), and h(I) = sum_k detune_k i_k - xi_k / 2 i_k (i_k - 1) - sum_{k<l} xikl i_k i_l
+  for (int k = 0; k < Q; k++) {
+    if (d_transfreq) d_transfreq[k] = 2.0 * M_PI * s[k];
+    if (d_selfkerr) d_selfkerr[k] = -M_PI * s[Q + k];
+  }
+  for (int p = 0; p < np; p++)
+    if (d_crosskerr) d_crosskerr[p] = -2.0 * M_PI * s[2 * Q + p];
+  return QD_OK;
+}
