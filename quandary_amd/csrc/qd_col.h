@@ -78,11 +78,11 @@ enum : int { KET_NONE = 0, KET_BOTTOM = 1, KET_INTERIOR = 2, KET_TOP = 3 };
 #ifndef QD_COL_GAUGE
 #define QD_COL_GAUGE 1
 #endif
-// Where that form issues the load of a sub-step's row phasor from the phasor table (qd_gauge.h; k_forward): 0 = at the top of the
-// sub-step, beside the scalar loads of its control row, consumed at the rotation in; 1 = the NEXT sub-step's right behind the pass loop,
-// covered by the rotation out and the penalty block (four registers live across the step tail, never across the pass loop)
-#ifndef QD_COL_GAUGE_AHEAD
-#define QD_COL_GAUGE_AHEAD 0
+// Where the frame change takes the relative phasors of the wave's COLUMNS from: 1 = the table row through the scalar path (the columns
+// of a wave's slots are contiguous there and their address is wave-uniform, like r_k); 0 = lanes of the row-phasor register (four
+// v_readlane per slot)
+#ifndef QD_COL_GAUGE_SCOL
+#define QD_COL_GAUGE_SCOL 1
 #endif
 
 // The model constants ColLean::init derives a kernel's values from, read from the kernel argument (every form but QD_COL_VARS)
@@ -508,9 +508,6 @@ struct ColTeam {
   int kc;  // KCLS: the wave's ket class
   // GAUGE: stage() solves in the frame where the drive is real (diagonal-split form without coupling)
   static constexpr bool GAUGE = QD_COL_GAUGE && SPLIT && !HJ;
-  // its LDS: one 16-byte word per thread behind the column table, where the thread parks its row phasor during the solve
-  static __host__ __device__ unsigned gauge_off(int N) { return ST::tab_off(N) + 48u * (unsigned)ST::ncols(N); }
-  static __host__ __device__ size_t gauge_lds_extra(int threads) { return GAUGE ? 16 * (size_t)threads : 0; }
   double* red;
   float4* fred;  // two slots of 16 partial sums of the solver's fp32 norm reduction
   int redslot, nw;
@@ -767,17 +764,19 @@ struct ColTeam {
   }
 
   // GAUGE: what a sub-step reads from the phasor table (qd_gauge.h), row = the table row of the sub-step: r_k through the scalar path
-  // like the control row (load_step_k), the thread's row phasor as one 16-byte load - lane = row of rho; the padding rows hold 1
+  // like the control row (load_step_k), a thread's row phasor as one 16-byte load - lane = row of rho; the padding rows hold 1.
+  // row: the table row itself (wave-uniform), from which stage() fetches the phasors it needs behind the pass loop
   struct GaugeRow {
     double r[Q];
-    double2 w;
+    const double* row;
   };
   static __device__ __forceinline__ void gauge_load_r(const double* row, GaugeRow& g) {
 #pragma unroll
     for (int k = 0; k < Q; k++) g.r[k] = kload(row + GAUGE_R + k);
   }
-  static __device__ __forceinline__ double2 gauge_load_w(const double* row) {
-    const col_d2 t = *(reinterpret_cast<const col_d2*>(row) + __lane_id());
+  // the thread's phasor of a 64-lane block of a table row: blk = row (the absolute w_i) or row + GAUGE_V (the relative v_i)
+  static __device__ __forceinline__ double2 gauge_load_w(const double* blk) {
+    const col_d2 t = *(reinterpret_cast<const col_d2*>(blk) + __lane_id());
     return make_double2(t.x, t.y);
   }
 
@@ -804,32 +803,28 @@ struct ColTeam {
   // unitary, so iterate m of the rotated solve is U z_m U^dag and the update norms are the ones of the lab frame up to rounding: same
   // stopping rule, same pass counts.  The controls are constant within a sub-step, so this is exact for any phase jump between
   // sub-steps.  r_k and the row phasors w_i depend on the control row and the row index only: they come from the phasor table built
-  // with the control table (qd_gauge.h, k_gauge; lane i reads w_i) - the column phasors of a wave's slots are lanes of the same
-  // register.  Per sub-step every wave rotates x in, and after the solve rotates out; the
-  // element phasors are formed again there from the row phasor parked in LDS, not kept in registers across the pass loop.  For these
-  // forms stage() also makes the step: on exit x = x_{n+1} = U^dag (2 z~ - x~) U, and z = U^dag z~ U where the stages are stored
-  // (A.ztraj); the caller neither publishes x nor combines.  Everything outside sees lab-frame values only, and a sub-step stays a
-  // function of the lab state and the control row: sliced, chunked and batched sweeps keep their bits.
+  // with the control table (qd_gauge.h, k_gauge).
+  // The frame PERSISTS between sub-steps.  x is the state in the frame of the sub-step on entry (the sweep rotates the initial
+  // condition in once, with w(0): k_forward), and stage() also makes the step and changes frame in one go: on exit
+  //   x = x~(s + 1) = f_rel o (2 z~ - x~),   f_rel = v_row conj(v_col),   v_i(s) = w_i(s + 1) conj(w_i(s))   (the table's second block),
+  // the next sub-step's right-hand side in ITS frame - the rotation out of s and into s + 1 are two diagonal unitaries back to back,
+  // applied as their product: one phasor per element and sub-step, and nothing of the frame exists across the pass loop.  w(nsub) = 1:
+  // the last sub-step leaves x in the lab frame.  THE RULE: x advances through the relative phasors only, by this one arithmetic path,
+  // whatever else the launch stores; lab-frame values - the trajectory row and the weighted Jtrace / Jfrobenius penalties (k_forward),
+  // the stored stage z = U^dag z~ U (here, A.ztraj only) - are by-products formed with the absolute phasor w(s), loaded only by the
+  // launches that need them, and never feed back into x.  So a sweep returns the same bits with and without storage, and a time slice
+  // hands on the rotated state as computed (k_forward): sliced and batched sweeps keep the bits of the unsliced single one.  The
+  // caller neither publishes x nor combines.
   // r_k^2 below 1e-280 counts as no drive (u_k = 1, r_k = 0: gauge_osc of qd_gauge.h): never a NaN.
-  // g: r_k and the thread's row phasor of this sub-step, from the phasor table (gauge_load_r / gauge_load_w); gnext: where stage() is to
-  // fetch the next sub-step's row phasor into g.w behind the pass loop (QD_COL_GAUGE_AHEAD), or null.  Both unused without GAUGE.
-  __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, double2 (&x)[EPT], double2 (&z)[EPT], GaugeRow& g,
-                                       const double* gnext) {
+  // g: the table row of this sub-step and its r_k (gauge_load_r).  Unused without GAUGE.
+  __device__ __forceinline__ int stage(const SweepArgs& A, const StepC<Q>& c, double alpha, double2 (&x)[EPT], double2 (&z)[EPT], const GaugeRow& g) {
     double sc = A.inv_abs2 / (alpha * alpha);
     if constexpr (KCLS) sc = to_scalar(sc);  // (wave-uniform: a scalar operand of the tested passes instead of a register pair of every pass)
     StepC<Q> ca = c;  // (alpha p, alpha q, alpha cs, alpha sn: scaled in VALU once per sub-step, back to scalar registers)
     if constexpr (GAUGE) {
 #pragma unroll
       for (int k = 0; k < Q; k++) ca.q[k] = to_scalar(fma(alpha, g.r[k], 0.0));  // alpha r_k (a silent oscillator: + 0.0, also under alpha < 0)
-      const double2 w = g.w;
-      st.st(gauge_slot(), w);
-#pragma unroll
-      for (int j = 0; j < EPT; j++) {
-        const double2 f = phasor(w, j), v = x[j];
-        x[j] = make_double2(fma(f.x, v.x, -f.y * v.y), fma(f.x, v.y, f.y * v.x));  // x~ = f x
-        slot_fence_pin<EPT>(x[j]);  // (one slot's phasor at a time)
-      }
-      publish(x);
+      publish(x);  // z_{-1} = x~, as the previous sub-step left it
     }
 #pragma unroll
     for (int k = 0; k < (SPLIT && !GAUGE ? Q : 0); k++) {
@@ -859,32 +854,50 @@ struct ColTeam {
     }
     if (SKIP) lastn = iter + 1;
     if constexpr (GAUGE) {
-      if (QD_COL_GAUGE_AHEAD && gnext) g.w = gauge_load_w(gnext);
-      const double2 w = st.ld(gauge_slot());
+      // (fetched here, behind the pass loop: nothing of the frame is held in a register or parked in LDS across the loop - a phasor
+      //  fetched at the top of the sub-step and parked costs 32 B more scratch than the kernel had, profiles/relframe_kres.txt)
+      const double2 v = gauge_load_w(g.row + GAUGE_V);
+      // (the relative phasors of the wave's columns: scalar loads of the same block, or lanes of v)
+      double2 vc[QD_COL_GAUGE_SCOL ? EPT : 1];
+      if constexpr (QD_COL_GAUGE_SCOL) {
+#pragma unroll
+        for (int j = 0; j < EPT; j++) vc[j] = make_double2(kload(g.row + GAUGE_V + 2 * (st.col0 + j)), kload(g.row + GAUGE_V + 2 * (st.col0 + j) + 1));
+      }
       const bool stages = A.ztraj != nullptr;
+      double2 w = make_double2(1.0, 0.0);
+      if (stages) w = gauge_load_w(g.row);
 #pragma unroll
       for (int j = 0; j < EPT; j++) {
-        const double2 f = phasor(w, j);
+        const double2 f = QD_COL_GAUGE_SCOL ? phasor(v, vc[QD_COL_GAUGE_SCOL ? j : 0]) : phasor(v, j);  // f_rel = v_row conj(v_col)
         const double tx = fma(2.0, z[j].x, -x[j].x), ty = fma(2.0, z[j].y, -x[j].y);
-        x[j] = make_double2(fma(f.x, tx, f.y * ty), fma(f.x, ty, -f.y * tx));  // conj(f) (2 z~ - x~)
-        if (stages) z[j] = make_double2(fma(f.x, z[j].x, f.y * z[j].y), fma(f.x, z[j].y, -f.y * z[j].x));
-        slot_fence_pin<EPT>(x[j]);
+        x[j] = make_double2(fma(f.x, tx, -f.y * ty), fma(f.x, ty, f.y * tx));  // x~(s + 1) = f_rel (2 z~ - x~)
+        if (stages) {  // by-product: the lab-frame stage conj(f_abs) z~
+          const double2 fa = phasor(w, j);
+          z[j] = make_double2(fma(fa.x, z[j].x, fa.y * z[j].y), fma(fa.x, z[j].y, -fa.y * z[j].x));
+        }
+        slot_fence_pin<EPT>(x[j]);  // (one slot's phasor at a time)
       }
     }
     return iter + 1;
   }
-  // GAUGE: LDS byte address of the thread's parked row phasor, from the wave's column block and the lane id - nothing of it is held in a
-  // vector register across the pass loop
-  __device__ __forceinline__ unsigned gauge_slot() const {
-    return gauge_off(st.N) + (unsigned)(st.col0 / EPT) * 1024u + __lane_id() * 16u;
+  // GAUGE: phasor w_row conj(w_col) of the thread's element; w = the thread's row phasor, wc = the one of the element's column
+  static __device__ __forceinline__ double2 phasor(const double2 w, const double2 wc) {
+    return make_double2(fma(w.x, wc.x, w.y * wc.y), fma(w.y, wc.x, -w.x * wc.y));
   }
-  // GAUGE: phasor w_row conj(w_col) of the thread's element in slot j; w = the row phasors, one per lane - the one of column col0 + j
-  // is lane col0 + j of the same register (idle columns and padding rows: 1)
+  // ... of the thread's element in slot j, w = the row phasors of one 64-lane block, one per lane: the one of column col0 + j is lane
+  // col0 + j of the same register (idle columns and padding rows: 1)
   __device__ __forceinline__ double2 phasor(const double2 w, int j) const {
     const int lc = st.col0 + j;
     const double cr = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(w.x), lc), __builtin_amdgcn_readlane(__double2loint(w.x), lc));
     const double ci = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(w.y), lc), __builtin_amdgcn_readlane(__double2loint(w.y), lc));
-    return make_double2(fma(w.x, cr, w.y * ci), fma(w.y, cr, -w.x * ci));
+    return phasor(w, make_double2(cr, ci));
+  }
+  // GAUGE: into the frame (IN: x~ = f x) or out of it (conj(f) x~) with the thread's absolute row phasor w - the one entry of a sweep
+  // (k_forward, slice 0) and its lab-frame by-products
+  template <bool IN>
+  __device__ __forceinline__ double2 rotate(const double2 w, int j, const double2 v) const {
+    const double2 f = phasor(w, j);
+    return IN ? make_double2(fma(f.x, v.x, -f.y * v.y), fma(f.x, v.y, f.y * v.x)) : make_double2(fma(f.x, v.x, f.y * v.y), fma(f.x, v.y, -f.y * v.x));
   }
   // the pass loop of stage() in the form of ket class KC (ColLean::apply), on stage()'s own variables; returns the index of the last pass
   template <int KC>
@@ -1445,28 +1458,48 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
     }
   };
 
-  // (GAUGE: stage() solves in the real-drive frame; r_k and the thread's row phasor of a sub-step come from row s of the phasor table)
+  // (GAUGE: the sweep runs in the real-drive frame, which persists between sub-steps (ColTeam::stage): x is the state in the frame of
+  //  sub-step s at the top of the loop body, and row s of the phasor table gives r_k, the relative phasors that take x to the frame of
+  //  s + 1, and the absolute ones for the lab-frame by-products.  Slice 0 enters the frame here, once; every other slice picks up the
+  //  rotated state its predecessor left in the carry, as computed; the last sub-step of the sweep leaves x in the lab frame.)
   constexpr bool GAUGE = TM::GAUGE && !KRY;
   typename TM::GaugeRow grow;
   const double* gtab = GAUGE ? QD_COL_GAUGE_TAB(A, ic) : nullptr;
-  if constexpr (GAUGE && QD_COL_GAUGE_AHEAD) grow.w = TM::gauge_load_w(gtab + (size_t)s_lo * GAUGE_STRIDE);
+  if constexpr (GAUGE) {
+    if (sl == 0) {
+      const double2 w = TM::gauge_load_w(gtab);
+#pragma unroll
+      for (int j = 0; j < EPT; j++) x[j] = tm.template rotate<true>(w, j, x[j]);
+    }
+  }
   for (int s = s_lo; s < s_hi; s++) {
     StepC<Q> c;
     load_step_k<Q>(QD_COL_CTL(A, ic) + (size_t)s * A.cs, c, HJ);
     if constexpr (GAUGE) {
-      TM::gauge_load_r(gtab + (size_t)s * GAUGE_STRIDE, grow);
-      if constexpr (!QD_COL_GAUGE_AHEAD) grow.w = TM::gauge_load_w(gtab + (size_t)s * GAUGE_STRIDE);
+      grow.row = gtab + (size_t)s * GAUGE_STRIDE;
+      TM::gauge_load_r(grow.row, grow);
     }
     if (SPLIT) tm.template set_alpha<false, SPLIT && !KRY>(S, 0.5 * c.h);
-    if (A.traj) store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, x, true);
+    if (A.traj) {
+      if constexpr (GAUGE) {  // by-product: the lab-frame state conj(f_abs) x~
+        const double2 w = TM::gauge_load_w(grow.row);
+        double2 xl[EPT];
+#pragma unroll
+        for (int j = 0; j < EPT; j++) xl[j] = tm.template rotate<false>(w, j, x[j]);
+        store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, xl, true);
+      } else {
+        store_state(A.traj + ((size_t)s * A.nb + ic) * 2 * dim, x, true);
+      }
+    }
     // the sub-step in stage form (ColTeam::stage): x is the right-hand side of the solve and stays in registers
-    // (GAUGE: stage() publishes the rotated x itself, and returns with the step made)
+    // (GAUGE: stage() publishes x itself, and returns with the step made and the frame changed)
     if constexpr (!GAUGE) tm.publish(x);
-    // (GAUGE: on return x is x_{n+1} already, and z is the lab-frame stage ONLY where stages are stored (A.ztraj) - otherwise it is left in
-    //  the rotated frame of this sub-step and must not be read; the stage store below is its one consumer)
+    // (GAUGE: on return x is x_{n+1} in the frame of the next sub-step, and z is the lab-frame stage ONLY where stages are stored
+    //  (A.ztraj) - otherwise it is left in the rotated frame of this sub-step and must not be read; the stage store below is its one
+    //  consumer)
     double2 z[EPT];
     if constexpr (KRY) napply += tm.kry_stage(A, c, 0.5 * c.h, x, z);
-    else napply += tm.stage(A, c, 0.5 * c.h, x, z, grow, GAUGE && QD_COL_GAUGE_AHEAD && s + 1 < s_hi ? gtab + (size_t)(s + 1) * GAUGE_STRIDE : nullptr);
+    else napply += tm.stage(A, c, 0.5 * c.h, x, z, grow);
     if (A.ztraj && tm.st.rowok) {  // the primal stage, read back by the adjoint sweep instead of repeating this solve: private to
       // this kernel pair, kept interleaved (one 16-byte streaming access per element; qd_handle tags the layout: ztraj_fmt)
       col_d2* dst = reinterpret_cast<col_d2*>(A.ztraj) + ((size_t)s * A.nb + ic) * dim;
@@ -1505,11 +1538,17 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
           for (int j = 0; j < EPT; j++)
             if (tm.st.rowok && tm.st.colof(j) == tm.st.row) pen_local = fma(wrow, x[j].x, pen_local);
         } else if (tm.st.rowok) {
+          // (GAUGE: Jtrace and Jfrobenius read off-diagonal elements - by-product: the lab-frame state conj(f_abs) x~ with the absolute
+          //  phasor of the frame x is in now, the next sub-step's; behind the last sub-step that is the lab frame itself)
+          double2 wl = make_double2(1.0, 0.0);
+          if constexpr (GAUGE)
+            if (s + 1 < A.nsub) wl = TM::gauge_load_w(gtab + (size_t)(s + 1) * GAUGE_STRIDE);
 #pragma unroll
           for (int j = 0; j < EPT; j++)
             if (tm.st.colok(j)) {
               double jr = 0.0, ji = 0.0;
-              evalJ_part<true>(S, A.tg, ic, tm.st.elem_now(j), x[j], jr, ji);
+              const double2 xl = GAUGE ? tm.template rotate<false>(wl, j, x[j]) : x[j];
+              evalJ_part<true>(S, A.tg, ic, tm.st.elem_now(j), xl, jr, ji);
               pen_local += (A.tg.objective_type == QD_OBJ_JTRACE ? -1.0 : 1.0) * weight * A.dt * jr;
             }
         }
@@ -1781,9 +1820,7 @@ template <int Q, int EPT, bool SPLIT, bool USLOT, bool SKIP, bool KRY>
 static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
   const int threads = 64 * (ST::ncols(a.S.N) / EPT);
-  // (the forward stage solve in the rotated frame parks one phasor per thread: ColTeam::stage, GAUGE)
-  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N)
-                                                 : adjoint ? 0 : ColTeam<Q, EPT, SPLIT, USLOT, SKIP, QD_COL_HJ>::gauge_lds_extra(threads));
+  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0);
   auto kf = adjoint ? QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY> : QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;

@@ -444,7 +444,8 @@ __global__ void k_gmat(const DevSys S, const double* __restrict__ g0, const doub
 
 // ---------------------------------------------------------------------------------------------
 // phasor table of the real-drive frame of the lean column forward sweeps (qd_gauge.h: layout, and the arithmetic - gauge_osc,
-// gauge_row_phasor): one thread per (row of the control table, lane i < 64); the threads i < QD_MAX_OSC of a row also write r_i.
+// gauge_row_phasor, gauge_rel_phasor): one thread per (row of the control table, lane i < 64) forms w_i of its row and of the next one
+// (1 behind the last row of a table: the lab frame) and their relative phasor; the threads i < QD_MAX_OSC of a row also write r_i.
 // grid.y = parameter sets (launch_gauge_sets): set j reads table + j * ctl_set and writes gauge + j * gauge_set.
 // ---------------------------------------------------------------------------------------------
 __global__ void k_gauge(const DevSys S, const double* __restrict__ table, int cs, int nrows, double* __restrict__ gauge, size_t ctl_set,
@@ -457,6 +458,9 @@ __global__ void k_gauge(const DevSys S, const double* __restrict__ table, int cs
   const double2 w = gauge_row_phasor(S, r, i);
   out[2 * i] = w.x;
   out[2 * i + 1] = w.y;
+  const double2 v = gauge_rel_phasor(w, row + 1 < nrows ? gauge_row_phasor(S, r + cs, i) : make_double2(1.0, 0.0));
+  out[GAUGE_V + 2 * i] = v.x;
+  out[GAUGE_V + 2 * i + 1] = v.y;
   if (i < QD_MAX_OSC) {
     double2 u;
     out[GAUGE_R + i] = i < S.Q ? gauge_osc(r[2 + i], r[2 + S.Q + i], u) : 0.0;
