@@ -1903,6 +1903,13 @@ static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const
 // own control table.  A request they cannot serve - the Krylov solver, states that do not divide into sets - is an error, never another
 // kernel.
 static bool col_sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
+#if QD_COL_VARS
+// ... of the third form besides: the constants table, never a dense handle; a time-sliced forward sweep needs the carry buffer of the
+// penalty sums
+static bool col_vars_args_ok(const SweepArgs& a, bool adjoint) {
+  return col_sets_args_ok(a) && col_vars_tab(a) && !a.S.dense && (adjoint || !a.sched || col_vars_pen_carry(a));
+}
+#endif
 // One object per <Q, EPT> (QD_COL_SETS_Q, QD_COL_SETS_EPT on the command line: they compile side by side) holds that case's col_sweep and
 // with it its kernels; the object built without the two holds the unit's entry point, which reaches them through QD_COL_DISPATCH.
 template <int Q, int EPT>

@@ -13,9 +13,7 @@
 namespace qd {
 
 hipError_t launch_sweep_colj_vars(const SweepArgs& a, bool adjoint, hipStream_t st) {
-  // (a time-sliced forward sweep needs the carry buffer of the penalty sums)
-  if (!adjoint && a.sched && !col_vars_pen_carry(a)) return hipErrorInvalidValue;
-  if (!col_sets_args_ok(a) || !col_vars_tab(a) || a.S.dense || !a.S.hasJ) return hipErrorInvalidValue;
+  if (!col_vars_args_ok(a, adjoint) || !a.S.hasJ) return hipErrorInvalidValue;
   QD_COL_DISPATCH(a.S, QD_COLK(sweep_part), a, adjoint, st);
 }
 

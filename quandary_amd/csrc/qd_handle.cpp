@@ -1083,6 +1083,7 @@ SweepPlan qd_handle::plan_sweep(int nb, bool adjoint) const {
     p.tuner_poly = 1;
   }
   p.cfg = cfg;  // (cfg.gmres is now what the kernel runs: SweepArgs::use_gmres)
+  p.form = sens && adjoint ? Form::Sens : !sets ? Form::Plain : vars_tab ? Form::Vars : Form::Sets;
   const bool col = col_sweep(cfg, b, p.neumann_split);
   p.family = pick_family(cfg, !ee, col);
   p.team = cfg.var == 16 && cfg.team > 1 && !f32 ? cfg.team : 1;
@@ -1152,8 +1153,8 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
       set_gauge_tab(a, d_gauge.p, 0u);
     }
   }
-  if (sets && vars_tab) {  // a model-parameter ensemble: set j of the launch reads the block of variant batch_first + j
-    if (!p.sweeps_vars(opts) || S.dense)
+  if (p.form == Form::Vars) {  // a model-parameter ensemble: set j of the launch reads the block of variant batch_first + j
+    if (!p.form_built(opts) || S.dense || p.team != 1 || nb % sets != 0)
       return fail(QD_ERR_STATE, "model-parameter ensemble: only the diagonal-split stationary iteration of the lean column kernels, with option ensemble_general the general kernel family with one workgroup per state and, with option ensemble_lean, the stationary iterations of the lean slot and fp32-mixed families sweep several variants at once");
     set_col_vars_tab(a, vars_tab + (size_t)batch_first * col_vars_stride(S.Q, S.npairs));
   }
@@ -1196,12 +1197,13 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
   if (p.kry_doubles && (r = d_kry.ensure(p.kry_doubles))) return r;
   a.kry = p.kry_doubles ? d_kry.p : nullptr;
   if ((r = check_cfg(p.cfg))) return r;
-  if (sets && vars_tab && (!p.sweeps_vars(opts) || p.team != 1 || nb % sets != 0))
-    return fail(QD_ERR_STATE, "model-parameter ensemble: only the lean column kernels, the general kernel family (option ensemble_general) and the stationary iterations of the lean slot and fp32-mixed families (option ensemble_lean), one workgroup per state, sweep several variants at once");
-  if (sets && !vars_tab && (!p.sweeps_sets(opts) || p.team != 1 || nb % sets != 0))
+  if (p.form == Form::Sets && (!p.form_built(opts) || p.team != 1 || nb % sets != 0))
     return fail(QD_ERR_STATE, "parameter-set batch: only the general kernel family with one workgroup per state (standard model or user Hamiltonian) - and, with option batch_lean, the stationary iterations of the lean slot, fp32-mixed and lean column families - sweeps several sets at once");
   if (p.family == Family::F32 && S.hasJ && p.cfg.gmres)
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
+  // (the sensitivity form reads the stored stages: none under explicit Euler)
+  if (p.form == Form::Sens && (!p.form_built(opts) || sets || S.dense || sol.stepper == QD_STEPPER_EE || !ztraj_doubles(nb)))
+    return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state sweeps them (standard model, implicit-midpoint family, one control vector)");
   return QD_OK;
 }
 
@@ -1239,25 +1241,21 @@ int qd_handle::arm_slices(qd::SweepArgs& a, int nb, int which) {
   return QD_OK;
 }
 
-// the sweep kernel of a plan, forward or adjoint: each lean family picks its instantiation once for both directions
+// The sweep kernel of a plan, forward or adjoint, by (family, form): each lean family picks its instantiation once for both directions.
+// A form a family has no kernels for is an error, never another kernel.
 static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool adjoint, const TuneOpts& opts, hipStream_t st) {
+  typedef hipError_t (*slot_fn)(const SweepArgs&, bool, const TuneOpts&, hipStream_t);
+  typedef hipError_t (*col_fn)(const SweepArgs&, bool, hipStream_t);
+  // index Form: Plain, Sets, Vars, Sens
+  static const slot_fn f32[4] = {launch_sweep_f32, launch_sweep_f32_sets, launch_sweep_f32_vars, nullptr};
+  static const slot_fn slot[4] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, nullptr};
+  static const col_fn col[4] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, nullptr};
+  const int f = (int)plan.form;
   switch (plan.family) {
-    // (nb_set: the instantiations with one control table per set - a missing one is an error, never another kernel)
-    // (a constants table: the third form, one block of model constants per set and one control table - qd_col_vars.h)
-    case Family::F32:
-      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_f32_vars(a, adjoint, opts, st);
-      return a.nb_set ? launch_sweep_f32_sets(a, adjoint, opts, st) : launch_sweep_f32(a, adjoint, opts, st);
-    case Family::Slot:
-      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_lean64_vars(a, adjoint, opts, st);
-      return a.nb_set ? launch_sweep_lean64_sets(a, adjoint, opts, st) : launch_sweep_lean64(a, adjoint, opts, st);
-    case Family::Col:
-      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return launch_sweep_col_vars(a, adjoint, st);
-      return a.nb_set ? launch_sweep_col_sets(a, adjoint, st) : launch_sweep_col(a, adjoint, st);
-    default:  // General and Global: the variant says which; nb_set: the instantiations with one control table per set, or - a constants
-              // table - the third form, one block of model constants per set (qd_gen_vars.h)
-      if (a.nb_set && !a.S.dense && col_vars_tab(a)) return adjoint ? launch_adjoint_vars(a, plan.cfg, st) : launch_forward_vars(a, plan.cfg, st);
-      if (a.nb_set) return adjoint ? launch_adjoint_sets(a, plan.cfg, st) : launch_forward_sets(a, plan.cfg, st);
-      return adjoint ? launch_adjoint(a, plan.cfg, st) : launch_forward(a, plan.cfg, st);
+    case Family::F32: return f32[f] ? f32[f](a, adjoint, opts, st) : hipErrorInvalidValue;
+    case Family::Slot: return slot[f] ? slot[f](a, adjoint, opts, st) : hipErrorInvalidValue;
+    case Family::Col: return col[f] ? col[f](a, adjoint, st) : hipErrorInvalidValue;
+    default: return launch_general(plan.form, adjoint, a, plan.cfg, st);  // General and Global: the variant says which
   }
 }
 
@@ -1308,7 +1306,7 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   if (a.ztraj) ztraj_fmt = plan.stage_layout();
   take_kernel(0);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 0))) return r;
-  if (a.sched && sets && vars_tab) {  // a sliced launch of the variants form carries its penalty sums from slice to slice
+  if (a.sched && plan.form == Form::Vars) {  // a sliced launch of the variants form carries its penalty sums from slice to slice
     if ((r = d_pencarry.ensure((size_t)nb * COL_VARS_PEN_STRIDE))) return r;
     set_col_vars_pen_carry(a, d_pencarry.p);
   }
@@ -1501,20 +1499,17 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   a.jbar = djbar;
   a.coeff = d_coeff.p;
   const int nsens = sens_columns(S.Q);
-  if (sens) {  // the sensitivity form of the general family's adjoint sweep: never another kernel in its place
-    if (plan.family != Family::General || sets || S.dense || sol.stepper == QD_STEPPER_EE || !a.ztraj)
-      return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state sweeps them (standard model, implicit-midpoint family, one control vector)");
+  if (plan.form == Form::Sens) {  // the per-state sums of the sensitivity form
     if ((r = d_sens.ensure((size_t)nb * nsens)) || (r = d_senssum.ensure(nsens))) return r;
     a.S.tred = d_sens.p;
   }
   QD_HIP(hipEventRecord(ev2, stream));
   take_kernel(1);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 1))) return r;
-  if (sens) QD_HIP(launch_adjoint_sens(a, plan.cfg, stream));
-  else QD_HIP(launch_sweep(a, plan, true, opts, stream));
+  QD_HIP(launch_sweep(a, plan, true, opts, stream));
   last_kernel[1] = take_kernel(1);
   QD_HIP(hipEventRecord(ev3, stream));
-  if (sens) QD_HIP(launch_reduce_coeff(d_sens.p, nb, nsens, d_senssum.p, accumulate ? 1 : 0, stream));
+  if (plan.form == Form::Sens) QD_HIP(launch_reduce_coeff(d_sens.p, nb, nsens, d_senssum.p, accumulate ? 1 : 0, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_adj = a.sched != nullptr;
   if (sets) QD_HIP(launch_reduce_coeff_sets(d_coeff.p, nb / sets, (int)ncol, d_coeffsum.p, sets, stream));  // once per set, over its own states

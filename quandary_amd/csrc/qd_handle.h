@@ -91,6 +91,12 @@ struct HBuf {
 // Col: lean column kernels (qd_col.hip); Global: vectors in global memory, teams of workgroups (qd_big.h, variant 16).
 enum class Family { General = 0, F32 = 1, Slot = 2, Col = 3, Global = 4 };
 
+// Form of the sweep kernels, the second axis of the same decision (every family has the plain form, a missing one is an error):
+// Plain: one control vector, one set of model constants; Sets: one control table per parameter set (qd_handle::sets without a constants
+// table); Vars: one block of model constants per ensemble variant and one control table (sets with qd_handle::vars_tab); Sens: the adjoint
+// sweep of a single evaluation that also sums the model-constant sensitivities (qd_handle::sens).
+enum class Form : int { Plain = 0, Sets = 1, Vars = 2, Sens = 3 };
+
 // Gershgorin bounds of a row of M for the current parameters (qd_handle::row_bounds) and the largest alpha = |h| / 2 of the step
 // schedule: what every solver gate looks at, computed once per plan
 struct RowBound { double diag, off, amax; };
@@ -98,6 +104,7 @@ struct RowBound { double diag, off, amax; };
 // Everything the host decides about one sweep before it launches it (qd_handle::plan_sweep)
 struct SweepPlan {
   Family family;
+  Form form;           // from the handle's state when the plan is made: nothing downstream looks at the sweep's arguments to find it out
   LaunchCfg cfg;       // final configuration (a stand-in for GMRES has re-picked it)
   int solver;          // QD_SOLVER_*: the iteration that solves the linear systems (qd_last_solver)
   int neumann_split, stop_residual, maxiter_factor;  // SweepArgs fields of the same names (maxiter: x linearsolver_maxiter); use_gmres = cfg.gmres
@@ -111,20 +118,26 @@ struct SweepPlan {
   bool need_big;       // ensure_big before the launch
   // the global-memory kernels store the stages in the element order of the general ones
   Family stage_layout() const { return family == Family::Global ? Family::General : family; }
-  // Kernels with a set axis exist for this plan (parameter-set batch): the general family - the standard model and the dense user
-  // Hamiltonians of the LDS kernels alike -, and under option batch_lean the lean slot, fp32-mixed and lean column families where the
-  // kernel's solver is a stationary iteration (their Krylov kernels have no SETS form)
-  bool sweeps_sets(const TuneOpts& o) const {
-    return family == Family::General || (o.batch_lean && (family == Family::Slot || family == Family::F32 || family == Family::Col) && cfg.gmres == 0);
-  }
-  // Kernels that read one block of model constants per set exist for this plan (model-parameter ensemble on a standard-model handle):
-  // the diagonal-split stationary iteration of the lean column family (k_*_col_vars), and under option ensemble_general the general
-  // family - Neumann and both direct Krylov forms (k_forward_vars / k_adjoint_vars) -, under option ensemble_lean the lean slot and
-  // fp32-mixed families where the kernel's solver is a stationary iteration (k_forward_q32_vars / k_adjoint_q32_vars: a neumann request
-  // or a gmres request served by the Neumann stand-in; their Krylov kernels have no variants form)
-  bool sweeps_vars(const TuneOpts& o) const {
-    return (family == Family::Col && cfg.gmres == 0 && neumann_split) || (family == Family::General && o.ensemble_general) ||
-           (o.ensemble_lean && (family == Family::Slot || family == Family::F32) && cfg.gmres == 0);
+  // Kernels of the plan's form exist for its family and solver:
+  // Sets: the general family - the standard model and the dense user Hamiltonians of the LDS kernels alike -, and under option batch_lean
+  //   the lean slot, fp32-mixed and lean column families where the kernel's solver is a stationary iteration (their Krylov kernels have
+  //   no SETS form);
+  // Vars: the diagonal-split stationary iteration of the lean column family (k_*_col_vars), under option ensemble_general the general
+  //   family - Neumann and both direct Krylov forms (k_forward_vars / k_adjoint_vars) -, under option ensemble_lean the lean slot and
+  //   fp32-mixed families where the kernel's solver is a stationary iteration (k_forward_q32_vars / k_adjoint_q32_vars: a neumann request
+  //   or a gmres request served by the Neumann stand-in; their Krylov kernels have no variants form);
+  // Sens: the general family (k_adjoint_sens).
+  bool form_built(const TuneOpts& o) const {
+    const bool slot = family == Family::Slot || family == Family::F32, stationary = cfg.gmres == 0;
+    switch (form) {
+      case Form::Plain: return true;
+      case Form::Sets: return family == Family::General || (o.batch_lean && (slot || family == Family::Col) && stationary);
+      case Form::Vars:
+        return (family == Family::Col && stationary && neumann_split) || (family == Family::General && o.ensemble_general) ||
+               (o.ensemble_lean && slot && stationary);
+      case Form::Sens: return family == Family::General;
+    }
+    return false;
   }
 };
 

@@ -66,40 +66,55 @@ constexpr bool kLind = (QD_L != 0);
   return hipLaunchCooperativeKernel(kern, dim3(teams * b.S.team), dim3(cfg.block), args, (unsigned)cfg.lds, st);
 }
 
+// The unit's form of the LDS sweep kernels (one workgroup per state), in the unit's direction: the kernel of <VAR, PLAIN> and the name
+// note_kernel records for it.  k_forward / k_adjoint carry the SETS flag as their seventh argument, recorded for the SETS form only.
+constexpr int kRole = (QD_PART & 1);  // 0 forward sweep, 1 adjoint sweep (note_kernel, plain_sweep)
+#if QD_VARS
+constexpr const char* kFormName = kRole ? "k_adjoint_vars" : "k_forward_vars";
+#elif QD_SENS
+constexpr const char* kFormName = "k_adjoint_sens";
+#else
+constexpr const char* kFormName = kRole ? "k_adjoint" : "k_forward";
+#endif
+template <int VAR, bool PLAIN>
+constexpr auto form_kernel() {
+#if QD_VARS && (QD_PART == 0 || QD_PART == 2)
+  return k_forward_vars<QD_Q, kLind, VAR, kQubit, kGmPart, PLAIN>;
+#elif QD_VARS
+  return k_adjoint_vars<QD_Q, kLind, VAR, kQubit, kGmPart, PLAIN>;
+#elif QD_SENS
+  return k_adjoint_sens<QD_Q, kLind, VAR, kQubit, kGmPart, PLAIN>;
+#elif QD_PART == 0 || QD_PART == 2
+  return k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, PLAIN, kSets>;
+#else
+  return k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, PLAIN, kSets>;
+#endif
+}
+// the launch sequence of every form and both directions (the general instantiation named before the PLAIN one)
+template <int VAR>
+static hipError_t go_lds(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  auto kf = form_kernel<VAR, false>();
+  bool plain = false;
+  if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
+    plain = plain_sweep(a, cfg, kRole);
+    if (plain) kf = form_kernel<VAR, true>();
+  }
+  hipError_t e = set_lds(kf, cfg.lds);
+  if (e != hipSuccess) return e;
+  if constexpr (kSets) note_kernel(kRole, kFormName, QD_Q, kLind, VAR, kQubit, kGmPart, plain, true);
+  else note_kernel(kRole, kFormName, QD_Q, kLind, VAR, kQubit, kGmPart, plain);
+  hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
+  return hipGetLastError();
+}
+
 #if QD_PART == 0 || QD_PART == 2
 template <int VAR>
 static hipError_t go_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
   if constexpr (VAR == 16 && !kSets && !kVars && variant_built(QD_Q, kLind, QD_B, VAR)) {
     note_kernel(0, "k_forward_big", QD_Q, kLind, kDense, kGmPart);
     return launch_big(reinterpret_cast<const void*>(k_forward_big<QD_Q, kLind, kDense, kGmPart>), a, cfg, st);
-#if QD_VARS
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_forward_vars<QD_Q, kLind, VAR, kQubit, kGmPart, false>;
-    bool plain = false;
-    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      plain = plain_sweep(a, cfg, 0);
-      if (plain) kf = k_forward_vars<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
-    }
-    hipError_t e = set_lds(kf, cfg.lds);
-    if (e != hipSuccess) return e;
-    note_kernel(0, "k_forward_vars", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
-    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
-    return hipGetLastError();
-#else
-  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, false, kSets>;
-    bool plain = false;
-    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      plain = plain_sweep(a, cfg, 0);
-      if (plain) kf = k_forward<QD_Q, kLind, VAR, kQubit, kGmPart, true, kSets>;
-    }
-    hipError_t e = set_lds(kf, cfg.lds);
-    if (e != hipSuccess) return e;
-    if constexpr (kSets) note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain, true);
-    else note_kernel(0, "k_forward", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
-    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
-    return hipGetLastError();
-#endif
+    return go_lds<VAR>(a, cfg, st);
   } else {
     return hipErrorInvalidValue;
   }
@@ -140,47 +155,8 @@ static hipError_t go_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream
     }
     note_kernel(1, "k_adjoint_big", QD_Q, kLind, kDense, kGmPart, false);
     return launch_big(reinterpret_cast<const void*>(k_adjoint_big<QD_Q, kLind, kDense, kGmPart, false>), a, cfg, st);
-#if QD_VARS
   } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_adjoint_vars<QD_Q, kLind, VAR, kQubit, kGmPart, false>;
-    bool plain = false;
-    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      plain = plain_sweep(a, cfg, 1);
-      if (plain) kf = k_adjoint_vars<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
-    }
-    hipError_t e = set_lds(kf, cfg.lds);
-    if (e != hipSuccess) return e;
-    note_kernel(1, "k_adjoint_vars", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
-    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
-    return hipGetLastError();
-#elif QD_SENS
-  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_adjoint_sens<QD_Q, kLind, VAR, kQubit, kGmPart, false>;
-    bool plain = false;
-    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      plain = plain_sweep(a, cfg, 1);
-      if (plain) kf = k_adjoint_sens<QD_Q, kLind, VAR, kQubit, kGmPart, true>;
-    }
-    hipError_t e = set_lds(kf, cfg.lds);
-    if (e != hipSuccess) return e;
-    note_kernel(1, "k_adjoint_sens", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
-    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
-    return hipGetLastError();
-#else
-  } else if constexpr (VAR != 16 && variant_built(QD_Q, kLind, QD_B, VAR)) {
-    auto kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, false, kSets>;
-    bool plain = false;
-    if constexpr ((VAR == 0 || VAR == 1) && !kGmPart) {
-      plain = plain_sweep(a, cfg, 1);
-      if (plain) kf = k_adjoint<QD_Q, kLind, VAR, kQubit, kGmPart, true, kSets>;
-    }
-    hipError_t e = set_lds(kf, cfg.lds);
-    if (e != hipSuccess) return e;
-    if constexpr (kSets) note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain, true);
-    else note_kernel(1, "k_adjoint", QD_Q, kLind, VAR, kQubit, kGmPart, plain);
-    hipLaunchKernelGGL(kf, dim3(a.nb), dim3(cfg.block), cfg.lds, st, a);
-    return hipGetLastError();
-#endif
+    return go_lds<VAR>(a, cfg, st);
   } else {
     return hipErrorInvalidValue;
   }

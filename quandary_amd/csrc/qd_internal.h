@@ -228,22 +228,19 @@ hipError_t launch_controls2(const DevCtlDesc& d, const double* params, const dou
                             unsigned long long* zero_me, hipStream_t st);
 hipError_t launch_apply(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb,
                         const LaunchCfg& cfg, hipStream_t st);
-hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-hipError_t launch_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-// the same sweeps with one control table per set of a.nb_set states (qd_inst.hip with -DQD_SETS=1): every LDS variant, of the standard
-// Hamiltonian model and of the dense user Hamiltonians (one G(t) table per set, a.gtab_set)
-hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-// ... with one block of model constants per set of a.nb_set states and ONE control table (qd_inst.hip with -DQD_VARS=1: k_forward_vars /
-// k_adjoint_vars, the template arguments of the kernel launch_forward / launch_adjoint pick for the same arguments; the table of
-// qd_col_vars.h in a.S.hcr, qd_gen_vars.h): the LDS variants of the standard Hamiltonian model, Neumann and GMRES kernels
-hipError_t launch_forward_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-hipError_t launch_adjoint_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
-// the sensitivity form of the adjoint sweep of a single evaluation (qd_inst.hip with -DQD_SENS=1: k_adjoint_sens, the template arguments
-// of the kernel launch_adjoint picks for the same arguments; qd_sens.h): besides the gradient coefficients the per-state sums
-// kbar^T (dM/d theta) z over all sub-steps for the detunings, self-Kerr and cross-Kerr coefficients, [nb][2 Q + npairs] into a.S.tred.
-// The LDS variants of the standard Hamiltonian model, implicit-midpoint family; anything else is an error
-hipError_t launch_adjoint_sens(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
+// The sweep kernels of the general family (qd_inst.hip) in the form the plan names (Form, qd_handle.h), forward or adjoint; every form runs
+// the template arguments the plain one picks for the same arguments:
+//   Plain  one control vector, one set of model constants - every variant, the global-memory kernels (variant 16) included
+//   Sets   one control table per set of a.nb_set states (-DQD_SETS=1): every LDS variant, of the standard Hamiltonian model and of the
+//          dense user Hamiltonians (one G(t) table per set, a.gtab_set)
+//   Vars   one block of model constants per set of a.nb_set states and ONE control table (-DQD_VARS=1: k_forward_vars / k_adjoint_vars,
+//          qd_gen_vars.h; the table of qd_col_vars.h in a.S.hcr): the LDS variants of the standard Hamiltonian model, Neumann and GMRES
+//   Sens   the adjoint sweep of a single evaluation that also sums kbar^T (dM/d theta) z over all sub-steps for the detunings, self-Kerr
+//          and cross-Kerr coefficients, [nb][2 Q + npairs] into a.S.tred (-DQD_SENS=1: k_adjoint_sens, qd_sens.h): the LDS variants of
+//          the standard Hamiltonian model, implicit-midpoint family, no forward sweep
+// A form that is not built for the arguments is an error, never another kernel.
+enum class Form : int;
+hipError_t launch_general(Form form, bool adjoint, const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 inline int sens_columns(int Q) { return 2 * Q + Q * (Q - 1) / 2; }
 // control tables of nset parameter vectors in one launch: params [nset][ndesign] -> table [nset][nrows][cs], table2 [nset][nrows2][cs]
 hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int ndesign, int nset, const double* times, const double* hs, int nrows,

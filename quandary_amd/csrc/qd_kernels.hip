@@ -19,6 +19,7 @@
 #include "qd_device.h"
 #include "qd_big.h"
 #include "qd_gauge.h"
+#include "qd_handle.h"  // (Form: the index of the dispatch table below)
 
 namespace qd {
 
@@ -700,19 +701,22 @@ void TuneOpts::load_env() {
 // ---------------------------------------------------------------------------------------------
 // dispatch to the per-(Q, Lindblad, qubit) translation units (qd_inst.hip)
 // ---------------------------------------------------------------------------------------------
-#define QD_DECL(q, l, b)                                                                                               \
-  hipError_t inst_forward_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);                             \
-  hipError_t inst_adjoint_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);                             \
+// The cases qd_inst.hip is built for, X(Q, L, B), written once: the standard Hamiltonian model (B = 0 general stencil: 1..8 oscillators;
+// B = 1 all-qubit stencil: Lindblad up to 5, Schroedinger up to 8 - beyond the reference's matrix-free templates, which stop at 5) and
+// the dense user-Hamiltonian operator (B = 2)
+#define QD_Q5(X, l, b) X(1, l, b) X(2, l, b) X(3, l, b) X(4, l, b) X(5, l, b)
+#define QD_Q8(X, l, b) QD_Q5(X, l, b) X(6, l, b) X(7, l, b) X(8, l, b)
+#define QD_CASES_MODEL(X) QD_Q8(X, 0, 0) QD_Q8(X, 1, 0) QD_Q8(X, 0, 1) QD_Q5(X, 1, 1)
+#define QD_CASES_DENSE(X) QD_Q8(X, 0, 2) QD_Q8(X, 1, 2)
+// every form of the sweep kernels (qd_internal.h, launch_general): Plain and Sets for every case, Vars and Sens - the latter the adjoint
+// sweep only - for the standard model
+#define QD_SWEEP(name, q, l, b) hipError_t name##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
+#define QD_DECL(q, l, b)                                                                          \
+  QD_SWEEP(inst_forward_, q, l, b) QD_SWEEP(inst_adjoint_, q, l, b) QD_SWEEP(inst_forwardsets_, q, l, b) QD_SWEEP(inst_adjointsets_, q, l, b) \
   hipError_t inst_apply_##q##_##l##_##b(const DevSys&, const double*, int, const double*, double*, int, const LaunchCfg&, hipStream_t);
-#define QD_DECL_Q(l, b) QD_DECL(1, l, b) QD_DECL(2, l, b) QD_DECL(3, l, b) QD_DECL(4, l, b) QD_DECL(5, l, b)
-QD_DECL_Q(0, 0) QD_DECL_Q(1, 0) QD_DECL_Q(0, 1) QD_DECL_Q(1, 1)
-// Schroedinger only: 6..8 oscillators (beyond the reference's matrix-free templates, which stop at 5)
-QD_DECL(6, 0, 0) QD_DECL(7, 0, 0) QD_DECL(8, 0, 0) QD_DECL(6, 0, 1) QD_DECL(7, 0, 1) QD_DECL(8, 0, 1)
-// ... and Lindblad on the general stencil [r5]
-QD_DECL(6, 1, 0) QD_DECL(7, 1, 0) QD_DECL(8, 1, 0)
-// dense user-Hamiltonian operator
-QD_DECL_Q(0, 2) QD_DECL_Q(1, 2)
-QD_DECL(6, 0, 2) QD_DECL(7, 0, 2) QD_DECL(8, 0, 2) QD_DECL(6, 1, 2) QD_DECL(7, 1, 2) QD_DECL(8, 1, 2)
+#define QD_DECL_MODEL(q, l, b) \
+  QD_SWEEP(inst_forwardvars_, q, l, b) QD_SWEEP(inst_adjointvars_, q, l, b) QD_SWEEP(inst_adjointsens_, q, l, b)
+QD_CASES_MODEL(QD_DECL) QD_CASES_DENSE(QD_DECL) QD_CASES_MODEL(QD_DECL_MODEL)
 
 #define QD_DECLT(q, l) hipError_t inst_bigtable_##q##_##l##_0(const DevSys&, double*, unsigned*, hipStream_t);
 QD_DECLT(1, 0) QD_DECLT(2, 0) QD_DECLT(3, 0) QD_DECLT(4, 0) QD_DECLT(5, 0) QD_DECLT(6, 0) QD_DECLT(7, 0) QD_DECLT(8, 0)
@@ -729,108 +733,44 @@ hipError_t launch_big_table(const DevSys& S, double* ecoef, unsigned* edig, hipS
 
 typedef hipError_t (*sweep_fn)(const SweepArgs&, const LaunchCfg&, hipStream_t);
 typedef hipError_t (*apply_fn)(const DevSys&, const double*, int, const double*, double*, int, const LaunchCfg&, hipStream_t);
-#define QD_ROW(base, l, b) {base##1_##l##_##b, base##2_##l##_##b, base##3_##l##_##b, base##4_##l##_##b, base##5_##l##_##b, nullptr, nullptr, nullptr}
-#define QD_ROW8(base, l, b) {base##1_##l##_##b, base##2_##l##_##b, base##3_##l##_##b, base##4_##l##_##b, base##5_##l##_##b, base##6_##l##_##b, base##7_##l##_##b, base##8_##l##_##b}
-// index [qubit][lindblad][Q-1]
-static const sweep_fn fwd_tab[3][2][8] = {{QD_ROW8(inst_forward_, 0, 0), QD_ROW8(inst_forward_, 1, 0)},
-                                          {QD_ROW8(inst_forward_, 0, 1), QD_ROW(inst_forward_, 1, 1)},
-                                          {QD_ROW8(inst_forward_, 0, 2), QD_ROW8(inst_forward_, 1, 2)}};
-static const sweep_fn adj_tab[3][2][8] = {{QD_ROW8(inst_adjoint_, 0, 0), QD_ROW8(inst_adjoint_, 1, 0)},
-                                          {QD_ROW8(inst_adjoint_, 0, 1), QD_ROW(inst_adjoint_, 1, 1)},
-                                          {QD_ROW8(inst_adjoint_, 0, 2), QD_ROW8(inst_adjoint_, 1, 2)}};
-static const apply_fn app_tab[3][2][8] = {{QD_ROW8(inst_apply_, 0, 0), QD_ROW8(inst_apply_, 1, 0)},
-                                          {QD_ROW8(inst_apply_, 0, 1), QD_ROW(inst_apply_, 1, 1)},
-                                          {QD_ROW8(inst_apply_, 0, 2), QD_ROW8(inst_apply_, 1, 2)}};
+// index [form][adjoint][stencil B][lindblad][Q-1]; a form that is not built for a case stays null
+struct InstTable {
+  sweep_fn sweep[4][2][3][2][8] = {};
+  apply_fn apply[3][2][8] = {};
+  constexpr InstTable() {
+#define QD_PUT(form, fwd, adj, q, l, b) sweep[(int)Form::form][0][b][l][q - 1] = fwd##q##_##l##_##b, sweep[(int)Form::form][1][b][l][q - 1] = adj##q##_##l##_##b;
+#define QD_PUT_ALL(q, l, b) \
+  QD_PUT(Plain, inst_forward_, inst_adjoint_, q, l, b) QD_PUT(Sets, inst_forwardsets_, inst_adjointsets_, q, l, b) apply[b][l][q - 1] = inst_apply_##q##_##l##_##b;
+#define QD_PUT_MODEL(q, l, b) \
+  QD_PUT(Vars, inst_forwardvars_, inst_adjointvars_, q, l, b) sweep[(int)Form::Sens][1][b][l][q - 1] = inst_adjointsens_##q##_##l##_##b;
+    QD_CASES_MODEL(QD_PUT_ALL) QD_CASES_DENSE(QD_PUT_ALL) QD_CASES_MODEL(QD_PUT_MODEL)
+  }
+};
+static constexpr InstTable inst_tab;
 
-// the SETS form of the same kernels (qd_inst.hip with -DQD_SETS=1), index [qubit][lindblad][Q-1] like the tables above
-#define QD_DECLS(q, l, b)                                                                        \
-  hipError_t inst_forwardsets_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t); \
-  hipError_t inst_adjointsets_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
-#define QD_DECLS_Q(l, b) QD_DECLS(1, l, b) QD_DECLS(2, l, b) QD_DECLS(3, l, b) QD_DECLS(4, l, b) QD_DECLS(5, l, b)
-QD_DECLS_Q(0, 0) QD_DECLS_Q(1, 0) QD_DECLS_Q(0, 1) QD_DECLS_Q(1, 1)
-QD_DECLS(6, 0, 0) QD_DECLS(7, 0, 0) QD_DECLS(8, 0, 0) QD_DECLS(6, 0, 1) QD_DECLS(7, 0, 1) QD_DECLS(8, 0, 1)
-QD_DECLS(6, 1, 0) QD_DECLS(7, 1, 0) QD_DECLS(8, 1, 0)
-QD_DECLS_Q(0, 2) QD_DECLS_Q(1, 2)
-QD_DECLS(6, 0, 2) QD_DECLS(7, 0, 2) QD_DECLS(8, 0, 2) QD_DECLS(6, 1, 2) QD_DECLS(7, 1, 2) QD_DECLS(8, 1, 2)
-static const sweep_fn fwd_sets_tab[3][2][8] = {{QD_ROW8(inst_forwardsets_, 0, 0), QD_ROW8(inst_forwardsets_, 1, 0)},
-                                               {QD_ROW8(inst_forwardsets_, 0, 1), QD_ROW(inst_forwardsets_, 1, 1)},
-                                               {QD_ROW8(inst_forwardsets_, 0, 2), QD_ROW8(inst_forwardsets_, 1, 2)}};
-static const sweep_fn adj_sets_tab[3][2][8] = {{QD_ROW8(inst_adjointsets_, 0, 0), QD_ROW8(inst_adjointsets_, 1, 0)},
-                                               {QD_ROW8(inst_adjointsets_, 0, 1), QD_ROW(inst_adjointsets_, 1, 1)},
-                                               {QD_ROW8(inst_adjointsets_, 0, 2), QD_ROW8(inst_adjointsets_, 1, 2)}};
-
-// a.nb states = a.nb / a.nb_set sets; a missing instantiation (the global-memory kernels, variant 16) is an error, never another kernel;
-// so is a dense operator without the stride of its G(t) tables
-hipError_t launch_forward_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 2 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
-      (cfg.qubit == 2) != (a.S.dense != 0) || (a.S.dense && (!a.S.gtab || !a.gtab_set)) || !fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
-    return hipErrorInvalidValue;
-  return fwd_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+// What a form asks of its arguments beyond a built instantiation.  Sets / Vars: a.nb states = a.nb / a.nb_set sets; no global-memory
+// kernels (variant 16); a dense operator comes with the stride of its G(t) tables (Sets) or not at all (Vars: the constants table in
+// a.S.hcr).  Sens: no set axis, an implicit-midpoint stepper, the stored stages and the output buffer.
+static bool form_args_ok(Form form, const SweepArgs& a, const LaunchCfg& cfg) {
+  const bool sets_axis = cfg.var != 16 && a.nb_set >= 1 && a.nb % a.nb_set == 0;
+  const bool model = (cfg.qubit == 0 || cfg.qubit == 1) && cfg.var != 16 && !a.S.dense && a.S.npairs == a.S.Q * (a.S.Q - 1) / 2;
+  switch (form) {
+    case Form::Plain: return true;
+    case Form::Sets: return sets_axis && (cfg.qubit == 2) == (a.S.dense != 0) && (!a.S.dense || (a.S.gtab && a.gtab_set));
+    case Form::Vars: return sets_axis && model && a.S.hcr != nullptr;
+    case Form::Sens: return model && a.nb_set == 0 && !a.stepper_ee && a.S.tred && a.ztraj;
+  }
+  return false;
 }
-hipError_t launch_adjoint_sets(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 2 || cfg.var == 16 || a.nb_set < 1 || a.nb % a.nb_set != 0 ||
-      (cfg.qubit == 2) != (a.S.dense != 0) || (a.S.dense && (!a.S.gtab || !a.gtab_set)) || !adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
-    return hipErrorInvalidValue;
-  return adj_sets_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
-}
-
-// the third form (qd_inst.hip with -DQD_VARS=1): one block of model constants per set, the table of qd_col_vars.h in a.S.hcr; the
-// standard Hamiltonian model only, index [qubit][lindblad][Q-1]
-#define QD_DECLV(q, l, b)                                                                        \
-  hipError_t inst_forwardvars_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t); \
-  hipError_t inst_adjointvars_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
-#define QD_DECLV_Q(l, b) QD_DECLV(1, l, b) QD_DECLV(2, l, b) QD_DECLV(3, l, b) QD_DECLV(4, l, b) QD_DECLV(5, l, b)
-QD_DECLV_Q(0, 0) QD_DECLV_Q(1, 0) QD_DECLV_Q(0, 1) QD_DECLV_Q(1, 1)
-QD_DECLV(6, 0, 0) QD_DECLV(7, 0, 0) QD_DECLV(8, 0, 0) QD_DECLV(6, 0, 1) QD_DECLV(7, 0, 1) QD_DECLV(8, 0, 1)
-QD_DECLV(6, 1, 0) QD_DECLV(7, 1, 0) QD_DECLV(8, 1, 0)
-static const sweep_fn fwd_vars_tab[2][2][8] = {{QD_ROW8(inst_forwardvars_, 0, 0), QD_ROW8(inst_forwardvars_, 1, 0)},
-                                               {QD_ROW8(inst_forwardvars_, 0, 1), QD_ROW(inst_forwardvars_, 1, 1)}};
-static const sweep_fn adj_vars_tab[2][2][8] = {{QD_ROW8(inst_adjointvars_, 0, 0), QD_ROW8(inst_adjointvars_, 1, 0)},
-                                               {QD_ROW8(inst_adjointvars_, 0, 1), QD_ROW(inst_adjointvars_, 1, 1)}};
-
-// a.nb states = a.nb / a.nb_set variants; a dense handle, variant 16, a missing table or a missing instantiation is an error
-static bool vars_args_ok(const SweepArgs& a, const LaunchCfg& cfg) {
-  return a.S.Q >= 1 && a.S.Q <= 8 && (cfg.qubit == 0 || cfg.qubit == 1) && cfg.var != 16 && a.nb_set >= 1 && a.nb % a.nb_set == 0 &&
-         !a.S.dense && a.S.hcr != nullptr && a.S.npairs == a.S.Q * (a.S.Q - 1) / 2;
-}
-hipError_t launch_forward_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (!vars_args_ok(a, cfg) || !fwd_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
-  return fwd_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
-}
-hipError_t launch_adjoint_vars(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (!vars_args_ok(a, cfg) || !adj_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
-  return adj_vars_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
-}
-
-// the sensitivity form of the adjoint sweep (qd_inst.hip with -DQD_SENS=1: k_adjoint_sens, qd_sens.h), index [qubit][lindblad][Q-1]: the
-// standard Hamiltonian model on the LDS variants, an implicit-midpoint stepper, one control table, the per-state sums into a.S.tred
-#define QD_DECLN(q, l, b) hipError_t inst_adjointsens_##q##_##l##_##b(const SweepArgs&, const LaunchCfg&, hipStream_t);
-#define QD_DECLN_Q(l, b) QD_DECLN(1, l, b) QD_DECLN(2, l, b) QD_DECLN(3, l, b) QD_DECLN(4, l, b) QD_DECLN(5, l, b)
-QD_DECLN_Q(0, 0) QD_DECLN_Q(1, 0) QD_DECLN_Q(0, 1) QD_DECLN_Q(1, 1)
-QD_DECLN(6, 0, 0) QD_DECLN(7, 0, 0) QD_DECLN(8, 0, 0) QD_DECLN(6, 0, 1) QD_DECLN(7, 0, 1) QD_DECLN(8, 0, 1)
-QD_DECLN(6, 1, 0) QD_DECLN(7, 1, 0) QD_DECLN(8, 1, 0)
-static const sweep_fn adj_sens_tab[2][2][8] = {{QD_ROW8(inst_adjointsens_, 0, 0), QD_ROW8(inst_adjointsens_, 1, 0)},
-                                               {QD_ROW8(inst_adjointsens_, 0, 1), QD_ROW(inst_adjointsens_, 1, 1)}};
-// a dense handle, variant 16, explicit Euler, a set axis, a missing output buffer or a missing instantiation is an error
-hipError_t launch_adjoint_sens(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || (cfg.qubit != 0 && cfg.qubit != 1) || cfg.var == 16 || a.nb_set != 0 || a.S.dense || a.stepper_ee || !a.S.tred ||
-      !a.ztraj || a.S.npairs != a.S.Q * (a.S.Q - 1) / 2 || !adj_sens_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1])
-    return hipErrorInvalidValue;
-  return adj_sens_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
-}
-
-hipError_t launch_forward(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || !fwd_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
-  return fwd_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
-}
-hipError_t launch_adjoint(const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
-  if (a.S.Q < 1 || a.S.Q > 8 || !adj_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1]) return hipErrorInvalidValue;
-  return adj_tab[cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1](a, cfg, st);
+hipError_t launch_general(Form form, bool adjoint, const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st) {
+  if ((int)form < 0 || (int)form > 3 || a.S.Q < 1 || a.S.Q > 8 || cfg.qubit < 0 || cfg.qubit > 2 || !form_args_ok(form, a, cfg)) return hipErrorInvalidValue;
+  const sweep_fn fn = inst_tab.sweep[(int)form][adjoint ? 1 : 0][cfg.qubit][a.S.lindblad ? 1 : 0][a.S.Q - 1];
+  return fn ? fn(a, cfg, st) : hipErrorInvalidValue;
 }
 hipError_t launch_apply(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb,
                         const LaunchCfg& cfg, hipStream_t st) {
-  if (S.Q < 1 || S.Q > 8 || !app_tab[cfg.qubit][S.lindblad ? 1 : 0][S.Q - 1]) return hipErrorInvalidValue;
-  return app_tab[cfg.qubit][S.lindblad ? 1 : 0][S.Q - 1](S, ctlrow, transpose, x, y, nb, cfg, st);
+  if (S.Q < 1 || S.Q > 8 || !inst_tab.apply[cfg.qubit][S.lindblad ? 1 : 0][S.Q - 1]) return hipErrorInvalidValue;
+  return inst_tab.apply[cfg.qubit][S.lindblad ? 1 : 0][S.Q - 1](S, ctlrow, transpose, x, y, nb, cfg, st);
 }
 
 hipError_t launch_controls(const DevCtlDesc& d, const double* params, const double* times, const double* hs, int nrows,

@@ -1026,7 +1026,7 @@ struct EnsembleCall {
   double* grad_mean;                 // [ndesign] (gradient mode): sum_j w[j] grads[j]
   // variants of the standard model's constants instead (qd_optim_eval(Grad)F_ensemble_model; norms is null): the caller has uploaded
   // their blocks (qd_handle::variants_upload, vars_tab) - launches are shared on the third form of the lean column kernels and, with
-  // option ensemble_general, of the general kernels, with option ensemble_lean of the lean slot and fp32-mixed kernels (SweepPlan::sweeps_vars)
+  // option ensemble_general, of the general kernels, with option ensemble_lean of the lean slot and fp32-mixed kernels (SweepPlan::form_built)
   bool model = false;
 };
 
@@ -1070,7 +1070,7 @@ static int batch_eval(qd_optim* o, const double* alphas, int nset, bool grad_mod
     // (a model-parameter ensemble: the diagonal-split stationary iteration of the lean column family - k_*_col_vars - whatever batch_lean says)
     // (... and, under option ensemble_general, the general family - k_forward_vars / k_adjoint_vars; never a dense handle: rejected by the caller)
     // (... and, under option ensemble_lean, the stationary iterations of the lean slot and fp32-mixed families - k_*_q32_vars)
-    const bool shares = ens && ens->model ? plan.sweeps_vars(h->opts) && !h->opts.ensemble_loop && !h->S.dense : plan.sweeps_sets(h->opts);
+    const bool shares = plan.form_built(h->opts) && !(plan.form == Form::Vars && (h->opts.ensemble_loop || h->S.dense));  // (Vars: ens->model)
     bool concurrent = shares && plan.team == 1 && (h->precision == QD_PRECISION_F64 || plan.family == Family::F32) &&
                       nset <= 65535 && h->batch_ctl_set() <= 0xffffffffull && h->batch_gtab_set() <= 0xffffffffull;
     if (concurrent) {

@@ -1595,75 +1595,52 @@ static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
   return a.nb <= 256 ? 1 : 2;
 }
 
+// What the unit's form asks of the sweep's arguments, and the name of its entry points.  Sets (parameter-set batch): a.nb states =
+// a.nb / a.nb_set sets, each reading its own control table.  Vars (model-parameter ensemble): the same axis, one control table, the
+// constants table in a.S.hcr - a dense handle or a missing table is an error.  Neither form has Krylov kernels (the degree tuner keeps
+// statistics per handle that a launch of mixed sets would blur): a request for one is an error, never another kernel.
 #if QD_VARS
-// The sweeps of a model-parameter ensemble: a.nb states = a.nb / a.nb_set variants, one control table, the constants table in a.S.hcr.
-// The instantiations are those of the SETS launchers below, picked by the same rules; no Krylov form is built: a request for one, a
-// dense handle or a missing table is an error, never another kernel.
-static bool vars_args_ok(const SweepArgs& a) {
+#define QD_Q32_ENTRY(name) name##_vars
+static bool form_args_ok(const SweepArgs& a) {
   return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0 && !a.S.dense && col_vars_tab(a) != nullptr && a.S.npairs == a.S.Q * (a.S.Q - 1) / 2;
 }
-hipError_t launch_sweep_f32_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
-  if (!vars_args_ok(a)) return hipErrorInvalidValue;
-  if (a.S.hasJ) {
-    if (a.S.Q == 5) return go_sweep<5, 1, float, false, true>(a, adjoint, st);
-    if (a.S.Q == 4) return go_sweep<4, 0, float, false, true>(a, adjoint, st);
-    return hipErrorInvalidValue;
-  }
-  if (a.S.Q == 5) return lean64_sb(a, o) == 1 ? go_sweep<5, 1, float>(a, adjoint, st) : go_sweep<5, 2, float>(a, adjoint, st);
-  if (a.S.Q == 4) return go_sweep<4, 0, float>(a, adjoint, st);
-  if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);
-  return hipErrorInvalidValue;
-}
-hipError_t launch_sweep_lean64_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
-  if (!vars_args_ok(a) || (a.S.Q != 4 && a.S.Q != 5)) return hipErrorInvalidValue;
-  if (a.S.Q == 4 && a.S.hasJ) return go_sweep<4, 0, double, false, true>(a, adjoint, st);
-  if (a.S.Q == 5 && a.S.hasJ) return go_sweep<5, 1, double, false, true>(a, adjoint, st);
-  if (a.S.Q == 4) return go_sweep<4, 0, double>(a, adjoint, st);
-  return lean64_sb(a, o) == 1 ? go_sweep<5, 1, double>(a, adjoint, st) : go_sweep<5, 2, double>(a, adjoint, st);
-}
 #elif QD_SETS
-// The sweeps of a parameter-set batch: a.nb states = a.nb / a.nb_set sets, each reading its own control table.  The instantiations are
-// those the launchers below pick for a stationary iteration; the Krylov kernels have no SETS form (their degree tuner keeps statistics
-// per handle that a launch of mixed sets would blur): a request for one is an error, never another kernel.
-static bool sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
-hipError_t launch_sweep_f32_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
-  if (!sets_args_ok(a)) return hipErrorInvalidValue;
-  if (a.S.hasJ) {
-    if (a.S.Q == 5) return go_sweep<5, 1, float, false, true>(a, adjoint, st);
-    if (a.S.Q == 4) return go_sweep<4, 0, float, false, true>(a, adjoint, st);
-    return hipErrorInvalidValue;
-  }
-  if (a.S.Q == 5) return lean64_sb(a, o) == 1 ? go_sweep<5, 1, float>(a, adjoint, st) : go_sweep<5, 2, float>(a, adjoint, st);
-  if (a.S.Q == 4) return go_sweep<4, 0, float>(a, adjoint, st);
-  if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);
-  return hipErrorInvalidValue;
-}
-hipError_t launch_sweep_lean64_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
-  if (!sets_args_ok(a) || (a.S.Q != 4 && a.S.Q != 5)) return hipErrorInvalidValue;
-  if (a.S.Q == 4 && a.S.hasJ) return go_sweep<4, 0, double, false, true>(a, adjoint, st);
-  if (a.S.Q == 5 && a.S.hasJ) return go_sweep<5, 1, double, false, true>(a, adjoint, st);
-  if (a.S.Q == 4) return go_sweep<4, 0, double>(a, adjoint, st);
-  return lean64_sb(a, o) == 1 ? go_sweep<5, 1, double>(a, adjoint, st) : go_sweep<5, 2, double>(a, adjoint, st);
-}
+#define QD_Q32_ENTRY(name) name##_sets
+static bool form_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
 #else
-hipError_t launch_sweep_f32(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+#define QD_Q32_ENTRY(name) name
+static bool form_args_ok(const SweepArgs&) { return true; }
+#endif
+// the Krylov instantiations (GM = true): compiled in the plain unit only
+#if QD_SETS || QD_VARS
+#define QD_Q32_KRYLOV(...)
+#else
+#define QD_Q32_KRYLOV(...) __VA_ARGS__
+#endif
+
+// The instantiation <Q, SB, R, GM, HJ> of a sweep, one chooser per precision for every form.  Stationary iterations: the uncoupled 2^5
+// system picks one or two elements per thread (lean64_sb); the Krylov kernels keep their basis in global memory (fp32: as float2,
+// Hessenberg problem in fp64).  (The order of the lines is the order in which the unit names its kernels: see go_sweep.)
+hipError_t QD_Q32_ENTRY(launch_sweep_f32)(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  if (!form_args_ok(a)) return hipErrorInvalidValue;
   if (a.S.hasJ) {  // [r6] dipole-dipole coupling: the coupled stencils in fp32 (stationary iterations only)
     if (a.use_gmres) return hipErrorInvalidValue;
     if (a.S.Q == 5) return go_sweep<5, 1, float, false, true>(a, adjoint, st);
     if (a.S.Q == 4) return go_sweep<4, 0, float, false, true>(a, adjoint, st);
     return hipErrorInvalidValue;
   }
-  if (a.use_gmres) {  // Krylov basis in global memory as float2, Hessenberg problem in fp64
+  QD_Q32_KRYLOV(if (a.use_gmres) {
     if (a.S.Q == 5) return go_sweep<5, 2, float, true>(a, adjoint, st);
     if (a.S.Q == 4) return go_sweep<4, 0, float, true>(a, adjoint, st);
     if (a.S.Q == 3) return go_sweep<3, 0, float, true>(a, adjoint, st);
     return hipErrorInvalidValue;
-  }
+  })
   if (a.S.Q == 5) return lean64_sb(a, o) == 1 ? go_sweep<5, 1, float>(a, adjoint, st) : go_sweep<5, 2, float>(a, adjoint, st);
   if (a.S.Q == 4) return go_sweep<4, 0, float>(a, adjoint, st);
   if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);  // [r3] 2x2x2 (BASELINE config 2): one wave per initial condition
   return hipErrorInvalidValue;
 }
+#if !QD_SETS && !QD_VARS  // (here, between the two choosers: the place of its kernels in the order the unit names them)
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
                             hipStream_t st) {
   if (mfma) {
@@ -1682,10 +1659,31 @@ hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose
   if (S.Q == 3) return go_app<3, 0, float>(S, ctlrow, transpose, x, y, nb, nrep, st);
   return hipErrorInvalidValue;
 }
+#endif
+// fp64 instantiation of the lean slot kernel: the sweeps of the 2^5 Lindblad system in QD_PRECISION_F64 and [r4] of the 2^4 one (the
+// 4-qubit open system: forward sweep 2.70 -> 2.46 ms against the general kernel, gradient evaluation equal; [r5] two waves of two
+// elements instead of four waves of one: 2.55 against 2.25 ms, not kept).  ([r6] the Krylov solver of these kernels - Team32::kry1 in
+// front of the plain GMRES - also on the coupled stencils.)  lean64_available admits Q = 4 | 5 only.
+hipError_t QD_Q32_ENTRY(launch_sweep_lean64)(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  if (!form_args_ok(a) || (a.S.Q != 4 && a.S.Q != 5)) return hipErrorInvalidValue;
+  if (a.S.Q == 4 && a.S.hasJ) {
+    QD_Q32_KRYLOV(if (a.use_gmres) return go_sweep<4, 0, double, true, true>(a, adjoint, st);)
+    return go_sweep<4, 0, double, false, true>(a, adjoint, st);
+  }
+  if (a.S.hasJ) {
+    QD_Q32_KRYLOV(if (a.use_gmres) return go_sweep<5, 1, double, true, true>(a, adjoint, st);)
+    return go_sweep<5, 1, double, false, true>(a, adjoint, st);
+  }
+  if (a.S.Q == 4) {  // 2^4: one element per thread, four waves
+    QD_Q32_KRYLOV(if (a.use_gmres) return go_sweep<4, 0, double, true>(a, adjoint, st);)
+    return go_sweep<4, 0, double>(a, adjoint, st);
+  }
+  if (lean64_sb(a, o) == 1) return go_sweep<5, 1, double>(a, adjoint, st);
+  QD_Q32_KRYLOV(if (a.use_gmres) return go_sweep<5, 2, double, true>(a, adjoint, st);)
+  return go_sweep<5, 2, double>(a, adjoint, st);
+}
 
-// fp64 instantiation of the lean slot kernel: the Neumann sweeps of the 2^5 Lindblad system in QD_PRECISION_F64 and [r4] of the 2^4
-// one (the 4-qubit open system: forward sweep 2.70 -> 2.46 ms against the general kernel, gradient evaluation equal; [r5] two waves of
-// two elements instead of four waves of one: 2.55 against 2.25 ms, not kept)
+#if !QD_SETS && !QD_VARS
 bool lean64_available(const DevSys& S, const TuneOpts& o) {
   // (dipole-dipole coupling [r5]: instantiations of their own - 2^4 one element per thread, 2^5 two; stationary iterations only)
   if (!S.lindblad || S.dense || (S.Q != 5 && S.Q != 4)) return false;
@@ -1693,20 +1691,12 @@ bool lean64_available(const DevSys& S, const TuneOpts& o) {
     if (S.n[k] != 2 || S.ness[k] != 2) return false;
   return !o.no_lean64;
 }
-hipError_t launch_sweep_lean64(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
-  // ([r6] the Krylov solver of these kernels - Team32::kry1 in front of the plain GMRES - also on the coupled stencils)
-  if (a.S.Q == 4 && a.S.hasJ) return a.use_gmres ? go_sweep<4, 0, double, true, true>(a, adjoint, st) : go_sweep<4, 0, double, false, true>(a, adjoint, st);
-  if (a.S.Q == 5 && a.S.hasJ) return a.use_gmres ? go_sweep<5, 1, double, true, true>(a, adjoint, st) : go_sweep<5, 1, double, false, true>(a, adjoint, st);
-  if (a.S.Q == 4) return a.use_gmres ? go_sweep<4, 0, double, true>(a, adjoint, st) : go_sweep<4, 0, double>(a, adjoint, st);  // 2^4: one element per thread, four waves
-  if (lean64_sb(a, o) == 1) return go_sweep<5, 1, double>(a, adjoint, st);
-  return a.use_gmres ? go_sweep<5, 2, double, true>(a, adjoint, st) : go_sweep<5, 2, double>(a, adjoint, st);
-}
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st) {
   if (S.Q == 4 && S.hasJ) return go_app<4, 0, double, true>(S, ctlrow, transpose, x, y, nb, 1, st);
   if (S.Q == 5 && S.hasJ) return go_app<5, 1, double, true>(S, ctlrow, transpose, x, y, nb, 1, st);
   if (S.Q == 4) return go_app<4, 0, double>(S, ctlrow, transpose, x, y, nb, 1, st);
   return go_app<5, 2, double>(S, ctlrow, transpose, x, y, nb, 1, st);
 }
-#endif  // QD_VARS, QD_SETS
+#endif  // !QD_SETS && !QD_VARS
 
 }  // namespace qd
