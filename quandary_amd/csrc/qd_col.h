@@ -40,6 +40,21 @@
 #if QD_COL_VARS
 #include "qd_col_vars.h"
 #endif
+// With QD_COL_SENS 1 (set by qd_col_sens.hip / qd_colj_sens.hip, objects of their own): the sensitivity form of the ADJOINT sweep,
+// k_adjoint_col_sens / k_adjoint_colj_sens (model-constant sensitivities, qd_optim_evalGradF_model with option sens_lean).  dM/d theta of a
+// detuning, a self-Kerr or a cross-Kerr coefficient is diagonal and time-independent, so d objective / d theta is a weighted sum over the
+// elements of W[e] = sum over the sub-steps of kbar_e.x z_e.y - kbar_e.y z_e.x, with the integer weights of qd_sens.h.  A thread keeps
+// W of its EPT elements in fp64 registers across the time loop - two fma per element and sub-step where kbar and z are at hand, nothing
+// per constant - and weights, reduces and stores the sens_count(Q) sums once per task, to the task's own row of SweepArgs::S.tred
+// [nslice][nb][sens_count(Q)] (no atomics: the host adds the rows in a fixed order).  Only the adjoint kernel of the diagonal-split
+// stationary instantiations is built; the forward sweep of the call is the plain k_forward_col / k_forward_colj.  Without the flag this
+// file preprocesses to the text it had before the form existed.
+#ifndef QD_COL_SENS
+#define QD_COL_SENS 0
+#endif
+#if QD_COL_SENS && (QD_COL_SETS || QD_COL_VARS)
+#error "QD_COL_SENS: a single evaluation - not together with QD_COL_SETS or QD_COL_VARS"
+#endif
 #if QD_COL_SETS || QD_COL_VARS
 #define QD_COL_CTL(A, ic) (A.ctl + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * A.ctl_set)
 #define QD_COL_GAUGE_TAB(A, ic) (gauge_tab(A) + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * gauge_set(A))
@@ -1633,6 +1648,12 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
     for (int j = 0; j < EPT; j++) xb[j] = tm.st.ok(j) ? make_double2(xbT[tm.st.elem(j)], xbT[dim + tm.st.elem(j)]) : make_double2(0.0, 0.0);
   }
   const double jbar_pen = A.jbar[ic * 3 + 0];
+#if QD_COL_SENS
+  // W of the thread's elements over the sub-steps of this task (the sensitivity form, see the top of the file)
+  double wacc[EPT];
+#pragma unroll
+  for (int j = 0; j < EPT; j++) wacc[j] = 0.0;
+#endif
   auto load_state = [&](const double* base, int s, double2(&dst)[EPT]) {
     const double* src = base + ((size_t)s * A.nb + ic) * 2 * dim;
 #pragma unroll
@@ -1716,6 +1737,14 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
         }
       }
       tm.publish(z);
+#if QD_COL_SENS
+      // kbar^T (dM/d theta) z of the diagonal model operators, before the weights: kbar (h-scaled) and z are in ONE frame here, the lab
+      // frame - the adjoint solve knows no other, and the forward sweep stores the stage as the lab-frame by-product z = U^dag z~ U
+      // whatever frame it solves in (ColTeam::stage, A.ztraj) - as the ladder contraction below already relies on.  Padding elements
+      // hold zeros in both.
+#pragma unroll
+      for (int j = 0; j < EPT; j++) wacc[j] = fma(kb[j].x, z[j].y, fma(-kb[j].y, z[j].x, wacc[j]));
+#endif
       // gradient coefficients x^T dM/dp_k z and x^T dM/dq_k z with x := kbar (mastereq.hpp:553-604)
 #pragma unroll
       for (int j = 0; j < EPT; j++) {
@@ -1751,6 +1780,22 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
         d0[dim + tm.st.elem(j)] = xb[j].y;
       }
   }
+#if QD_COL_SENS
+  {  // once per task: the integer weights of the thread's elements from their level digits (qd_sens.h), the workgroup totals, the row
+    constexpr int NS = sens_count(Q);
+    double sacc[NS];
+#pragma unroll
+    for (int i = 0; i < NS; i++) sacc[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+      const bool live = tm.st.ok(j);  // (a padding element has no digits and adds nothing)
+      unsigned bra = 0, ket = 0;
+      if (live) sens_decode<Q, true>(S, tm.st.elem(j), bra, ket);
+      sens_add<Q, true>(bra, ket, live ? wacc[j] : 0.0, sacc);
+    }
+    sens_store<NS>(tm, sacc, A.S.tred + ((size_t)sl * A.nb + ic) * NS);
+  }
+#endif
   if (A.sched) sched_done(A.sched, ic, (unsigned)(sl + 1), tm.lastna);
   }
 }
@@ -1821,7 +1866,13 @@ static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
   const int threads = 64 * (ST::ncols(a.S.N) / EPT);
   const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0);
+#if QD_COL_SENS
+  // (the sensitivity form has no forward kernel - the forward sweep of its call is the plain one: an error, and nothing instantiated)
+  if (!adjoint) return hipErrorInvalidValue;
+  auto kf = QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
+#else
   auto kf = adjoint ? QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY> : QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
+#endif
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
   note_kernel(adjoint ? 1 : 0, adjoint ? QD_COLK_NAME(k_adjoint) : QD_COLK_NAME(k_forward), Q, EPT, SPLIT, USLOT, SKIP, KRY);
@@ -1842,9 +1893,10 @@ static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-#if QD_COL_VARS
+#if QD_COL_VARS || QD_COL_SENS
   // the third form is built for the diagonal-split stationary iteration only (a plain-Neumann or Krylov plan goes variant by variant,
-  // qd_optim.cpp): anything else is an error, and nothing of it is instantiated
+  // qd_optim.cpp), and so is the sensitivity form (such a plan takes the general family, qd_optim_evalGradF_model): anything else is an
+  // error, and nothing of it is instantiated
   if (a.use_gmres || !a.neumann_split) return hipErrorInvalidValue;
   if constexpr (QD_COL_HJ) {
     return go(yes, no, no);
@@ -1898,11 +1950,20 @@ static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const
     return hipErrorInvalidValue;                                                       \
   } while (0)
 
-#if QD_COL_SETS || QD_COL_VARS
+#if QD_COL_SENS
+// The units of the sensitivity form: the adjoint sweep of a single evaluation on the diagonal-split stationary iteration, with the stored
+// stages and the buffer of the sums.  Anything else - a forward sweep included - is an error, never another kernel.
+static bool col_sens_args_ok(const SweepArgs& a, bool adjoint) {
+  return adjoint && !a.use_gmres && a.neumann_split && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && a.S.tred && a.ztraj;
+}
+#endif
+#if QD_COL_SETS || QD_COL_VARS || QD_COL_SENS
+#if !QD_COL_SENS
 // The SETS units (and the units of the third form, QD_COL_VARS: a set is a variant): a.nb states = a.nb / a.nb_set sets, each reading its
 // own control table.  A request they cannot serve - the Krylov solver, states that do not divide into sets - is an error, never another
 // kernel.
 static bool col_sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
+#endif
 #if QD_COL_VARS
 // ... of the third form besides: the constants table, never a dense handle; a time-sliced forward sweep needs the carry buffer of the
 // penalty sums

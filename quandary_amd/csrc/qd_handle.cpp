@@ -1203,7 +1203,7 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
   // (the sensitivity form reads the stored stages: none under explicit Euler)
   if (p.form == Form::Sens && (!p.form_built(opts) || sets || S.dense || sol.stepper == QD_STEPPER_EE || !ztraj_doubles(nb)))
-    return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state sweeps them (standard model, implicit-midpoint family, one control vector)");
+    return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state - and, with option sens_lean, the diagonal-split stationary iteration of the lean column family - sweeps them (standard model, implicit-midpoint family, one control vector)");
   return QD_OK;
 }
 
@@ -1249,7 +1249,7 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
   // index Form: Plain, Sets, Vars, Sens
   static const slot_fn f32[4] = {launch_sweep_f32, launch_sweep_f32_sets, launch_sweep_f32_vars, nullptr};
   static const slot_fn slot[4] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, nullptr};
-  static const col_fn col[4] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, nullptr};
+  static const col_fn col[4] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, launch_sweep_col_sens};
   const int f = (int)plan.form;
   switch (plan.family) {
     case Family::F32: return f32[f] ? f32[f](a, adjoint, opts, st) : hipErrorInvalidValue;
@@ -1498,18 +1498,20 @@ int qd_handle::adjoint_launch(const double* dxbarT, const double* djbar, int nb,
   a.xbarT = dxbarT;
   a.jbar = djbar;
   a.coeff = d_coeff.p;
-  const int nsens = sens_columns(S.Q);
-  if (plan.form == Form::Sens) {  // the per-state sums of the sensitivity form
-    if ((r = d_sens.ensure((size_t)nb * nsens)) || (r = d_senssum.ensure(nsens))) return r;
+  // the sums of the sensitivity form: one row per state - on the lean column family one per task, (time slice, state)
+  const int nsens = sens_columns(S.Q), sens_rows = nb * (plan.family == Family::Col ? col_slices(nb, tg.ntime, opts) : 1);
+  if (plan.form == Form::Sens) {
+    if ((r = d_sens.ensure((size_t)sens_rows * nsens)) || (r = d_senssum.ensure(nsens))) return r;
     a.S.tred = d_sens.p;
   }
   QD_HIP(hipEventRecord(ev2, stream));
   take_kernel(1);
   if (plan.family == Family::Col && (r = arm_slices(a, nb, 1))) return r;
+  if (plan.form == Form::Sens && nb * a.nslice != sens_rows) return fail(QD_ERR_STATE, "model-constant sensitivities: the time slices of the adjoint sweep are not those its buffer was sized for");
   QD_HIP(launch_sweep(a, plan, true, opts, stream));
   last_kernel[1] = take_kernel(1);
   QD_HIP(hipEventRecord(ev3, stream));
-  if (plan.form == Form::Sens) QD_HIP(launch_reduce_coeff(d_sens.p, nb, nsens, d_senssum.p, accumulate ? 1 : 0, stream));
+  if (plan.form == Form::Sens) QD_HIP(launch_reduce_coeff(d_sens.p, sens_rows, nsens, d_senssum.p, accumulate ? 1 : 0, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(reinterpret_cast<unsigned*>(h_sched.p) + 1, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_adj = a.sched != nullptr;
   if (sets) QD_HIP(launch_reduce_coeff_sets(d_coeff.p, nb / sets, (int)ncol, d_coeffsum.p, sets, stream));  // once per set, over its own states

@@ -180,6 +180,8 @@ struct TuneOpts {
                            // stationary iteration (k_forward_q32_vars / k_adjoint_q32_vars; 0 = variant by variant there, the default)
   int ensemble_loop = 0;   // "ensemble_loop": a model-parameter ensemble (qd_optim_evalF_ensemble_model / qd_optim_evalGradF_ensemble_model) goes variant by
                            // variant even where the lean column kernels could share its launches (A/B switch; 0 = share, the default)
+  int sens_lean = 0;       // "sens_lean": the model-constant sensitivities (qd_optim_evalGradF_model) stay on the lean column kernels where the adjoint plan is
+                           // their diagonal-split stationary iteration (k_adjoint_col_sens / k_adjoint_colj_sens; 0 = the general family everywhere, the default)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
   double sched_wait_s = 0.0;    // "sched_wait_s": seconds a time slice may wait for its predecessor (0 = automatic: 4 s x the processes that share the
                                 // device (QD_DEVICE_SHARERS, set by the launchers that put several ranks on one GPU) x the slice length in units of 1000 steps)
@@ -305,6 +307,12 @@ hipError_t launch_sweep_colj_sets(const SweepArgs& a, bool adjoint, hipStream_t 
 // to the second where S.hasJ.
 hipError_t launch_sweep_col_vars(const SweepArgs& a, bool adjoint, hipStream_t st);
 hipError_t launch_sweep_colj_vars(const SweepArgs& a, bool adjoint, hipStream_t st);
+// the sensitivity form of their adjoint sweep (qd_col_sens.hip / qd_colj_sens.hip: k_adjoint_col_sens, k_adjoint_colj_sens, the
+// instantiation launch_sweep_col picks for the same arguments): the diagonal-split stationary instantiations only, and the adjoint
+// direction only - a forward, Krylov or plain-Neumann request is an error.  Every task (state, time slice) stores its sums of
+// kbar^T (dM/d theta) z to its own row of a.S.tred, [nslice][nb][sens_columns(Q)].  The first forwards to the second where S.hasJ.
+hipError_t launch_sweep_col_sens(const SweepArgs& a, bool adjoint, hipStream_t st);
+hipError_t launch_sweep_colj_sens(const SweepArgs& a, bool adjoint, hipStream_t st);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false);
 size_t krylov_doubles(const DevSys& S, int nb);
 size_t big_work_doubles(const DevSys& S, int nb);

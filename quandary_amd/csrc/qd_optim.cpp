@@ -1361,19 +1361,26 @@ extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_
 // Model-constant sensitivities: the objective, its gradient and d objective / d (transfreq, selfkerr, crosskerr) from one forward and
 // one adjoint sweep.  The operators dM/d theta of these constants are diagonal and time-independent, so kbar^T (dM/d theta) z costs
 // one multiply-add per element and constant where the adjoint kernel forms the control-gradient coefficients from the same kbar and z
-// (qd_sens.h); kbar is never stored, so the sums cannot be formed anywhere else.  Only the general family has that kernel
+// (qd_sens.h); kbar is never stored, so the sums cannot be formed anywhere else.  The general family has that kernel for every system
 // (k_adjoint_sens): both sweeps are planned there, as options no_collean / no_lean64 would, and the handle is put back afterwards.
+// Under option sens_lean a call whose own plan is the diagonal-split stationary iteration of the lean column family stays on it: the
+// forward sweep as planned, the adjoint sweep on k_adjoint_col_sens / k_adjoint_colj_sens (qd_col.h under QD_COL_SENS), which keeps
+// w = kbar.x z.y - kbar.y z.x summed per element over the sub-steps and applies the integer weights once per task.
 // ---------------------------------------------------------------------------------------------------------------
 // leaves the handle on its own options, plan latch and tuner state however the call ends
+// latch0: the latch as it was before the caller asked the handle for its own plan (which may have decided it)
+// general: force the general family (false: the handle's own plan has a sensitivity form - options and latch stay as they are)
 struct SensScope {
   qd_handle* h;
   int no_collean, no_lean64, latch, poly[7];
   bool frozen;
-  explicit SensScope(qd_handle* hh)
-      : h(hh), no_collean(hh->opts.no_collean), no_lean64(hh->opts.no_lean64), latch(hh->sub_latch),
+  SensScope(qd_handle* hh, int latch0, bool general)
+      : h(hh), no_collean(hh->opts.no_collean), no_lean64(hh->opts.no_lean64), latch(latch0),
         poly{hh->poly_cur, hh->poly_lo, hh->poly_hi, hh->last_poly, hh->poly_steps, hh->fwd_poly, hh->poly_slow}, frozen(hh->poly_frozen) {
-    h->opts.no_collean = h->opts.no_lean64 = 1;
-    h->sub_latch = -1;  // (the gates decide for the forced family, as on a fresh handle with those options)
+    if (general) {
+      h->opts.no_collean = h->opts.no_lean64 = 1;
+      h->sub_latch = -1;  // (the gates decide for the forced family, as on a fresh handle with those options)
+    }
     h->sens = true;
   }
   ~SensScope() {
@@ -1384,7 +1391,7 @@ struct SensScope {
     h->poly_cur = poly[0], h->poly_lo = poly[1], h->poly_hi = poly[2], h->last_poly = poly[3], h->poly_steps = poly[4], h->fwd_poly = poly[5],
     h->poly_slow = poly[6], h->poly_frozen = frozen;
     h->params_dirty = true;
-    h->traj_valid = false;  // (the stored stages have the general family's layout)
+    h->traj_valid = false;  // (the stored stages have the general family's layout where that family was forced)
   }
 };
 
@@ -1405,8 +1412,22 @@ extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_obj
   const int Q = h->S.Q, np = h->S.npairs, nl = o->nlocal, ns = sens_columns(Q);
   int r;
   std::vector<double> s(ns);
+  // option sens_lean: both sweeps as the handle's own options plan them - where that is the lean column family and the adjoint plan has
+  // a sensitivity form (SweepPlan::form_built), the call stays there; anything else takes the general family as without the option
+  const int latch0 = h->sub_latch;
+  bool lean = false;
+  if (h->opts.sens_lean) {
+    if ((r = qd_set_params(h, alpha, h->ndesign))) return r;
+    PenaltyScope ps(h, o->pen);
+    StagesScope ss(h);
+    h->sens = true;  // (the adjoint plan names the form)
+    const SweepPlan pf = h->plan_sweep(nl, false), pa = h->plan_sweep(nl, true);
+    h->sens = false;
+    lean = pf.family == Family::Col && pa.family == Family::Col && pa.form == Form::Sens && pa.form_built(h->opts);
+    if (!lean) h->sub_latch = latch0;  // (what the gates decided for a plan that is not run is forgotten)
+  }
   {
-    SensScope scope(h);
+    SensScope scope(h, latch0, !lean);
     if ((r = qd_set_params(h, alpha, h->ndesign))) return r;
     {
       PenaltyScope ps(h, o->pen);
@@ -1414,8 +1435,8 @@ extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_obj
       const SweepPlan plan = h->plan_sweep(nl, false);
       if (plan.family == Family::Global)
         return fail(QD_ERR_UNSUPPORTED, who + ": the state does not fit one CU's LDS (dim > 4096) - the global-memory kernels have no sensitivity form");
-      if (plan.family != Family::General)
-        return fail(QD_ERR_UNSUPPORTED, who + ": the sweep is not planned on the general kernel family, the only one with a sensitivity form");
+      if (plan.family != (lean ? Family::Col : Family::General))
+        return fail(QD_ERR_UNSUPPORTED, who + ": the sweep is not planned on a kernel family with a sensitivity form (the general one; with option sens_lean the lean column one)");
       if (!trajectory_fits(h, nl, &o->tg))
         return fail(QD_ERR_UNSUPPORTED, who + ": the stored trajectory of the shard does not fit device memory and would be swept in chunks - not built for the sensitivity form");
     }
