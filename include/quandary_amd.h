@@ -470,12 +470,18 @@ int qd_optim_evalGradF_ensemble_model(qd_optim* o, const double* alpha, int nvar
  * sweep on its sensitivity form k_adjoint_col_sens / k_adjoint_colj_sens, which sums w per element over the sub-steps and weights the
  * sums once per task.  val and grad are then bit for bit those of qd_optim_evalGradF on that handle.  Any other plan - the lean column
  * Krylov kernels (gmres_split = 0), the plain Neumann form (neumann_split = 0), the lean slot systems - takes the general family as above.
+ * Option sens_slot = 1 (0 = default, under which nothing changes; deliberately a key of its own, sens_lean names the column family
+ * alone): where the handle's own plan puts both sweeps on the fp64 lean slot kernels (2^4 / 2^5 all-qubit Lindblad systems, with or
+ * without Jkl) and the adjoint sweep on their stationary iteration (a neumann request, or a gmres request served by the stand-in), the
+ * call stays there - the forward sweep on k_forward_q32 as planned, the adjoint sweep on k_adjoint_q32_sens of the same instantiation,
+ * which sums w per element over the sub-steps and weights the sums once per state.  val and grad are then bit for bit those of
+ * qd_optim_evalGradF on that handle.  A Krylov plan of that family (gmres_split = 0) takes the general family as above.
  * Errors: a null o, alpha, val or grad: QD_ERR_INVALID; a user-Hamiltonian handle or an objective created with nranks > 1:
  * QD_ERR_STATE; explicit Euler, QD_PRECISION_F32MIXED, a state beyond one CU's LDS (the global-memory kernels, dim > 4096), a shard
  * whose stored trajectory would need chunking, and whatever qd_optim_evalGradF rejects: QD_ERR_UNSUPPORTED, the message naming the
  * reason; no sweep is launched for any of them.
- * Not built: d / d Jkl (off-diagonal), d / d T1, T2, a sensitivity form of the lean slot kernels and of the Krylov and plain-Neumann
- * lean column kernels, sensitivities of an ensemble mean, several ranks. */
+ * Not built: d / d Jkl (off-diagonal), d / d T1, T2, a sensitivity form of the Krylov kernels of either lean family, of the
+ * plain-Neumann lean column kernels and of the fp32-mixed kernels, sensitivities of an ensemble mean, several ranks. */
 int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_objective_value* val, double* grad, double* d_transfreq,
                              double* d_selfkerr, double* d_crosskerr);
 
@@ -542,7 +548,8 @@ int qd_set_precision(qd_handle* h, int precision);
  * qd_optim_evalF_ensemble_model; 0 = default), ensemble_lean (... and on the stationary iterations of the lean slot and
  * fp32-mixed families; 0 = default), ensemble_loop (a model-parameter
  * ensemble goes variant by variant even where it could share launches: see qd_optim_evalF_ensemble_model; 0 = default), sens_lean (qd_optim_evalGradF_model
- * stays on the lean column kernels where their sensitivity form is built: see there; 0 = default).  Every key is also read from the
+ * stays on the lean column kernels where their sensitivity form is built: see there; 0 = default), sens_slot (... and on the fp64 lean
+ * slot kernels; 0 = default).  Every key is also read from the
  * environment variable QD_<KEY> once, at qd_create (tests, measurements).  Unknown keys: QD_ERR_INVALID. */
 int qd_set_option(qd_handle* h, const char* key, const char* value);
 int qd_get_precision(const qd_handle* h);

@@ -12,7 +12,11 @@ handles in one process, one with sens_lean = 1 and one with sens_lean = 0 (the g
 each after a warm-up.  Line "form": qd_last_adjoint_ms of evalGradF_model against plain evalGradF on the sens_lean = 1 handle - the cost
 of the form over the lean adjoint kernel.  Line "call": forward + adjoint device time and wall time of the whole evalGradF_model call,
 sens_lean = 1 against sens_lean = 0; spread = largest relative distance of a repetition from the best of its own three.
-usage: model_sens_probe.py [s33 l44 l333 l320 c4lean c4jlean ...] >> profiles/model_sens_probe.txt"""
+
+q4slot / c5slot / q4jslot: the same two lines for the sensitivity form of the lean slot adjoint (option sens_slot = 1: k_adjoint_q32_sens)
+on the workloads q4, c5 and q4j - 2^4, 2^5 and coupled 2^4 Lindblad, their 256 / 1024 / 256 basis initial conditions, 1000 steps -
+with the penalties on (optim_penalty = optim_penalty_energy = 0.1); the handles differ in sens_slot.
+usage: model_sens_probe.py [s33 l44 l333 l320 c4lean c4jlean q4slot c5slot q4jslot ...] >> profiles/model_sens_probe.txt"""
 import os
 import sys
 import time
@@ -31,15 +35,21 @@ PROBES = {
     "l320": ([3, 20], {**L, "nessential": [2, 2]}),
 }
 
-LEAN_PROBES = {"c4lean": {}, "c4jlean": {"Jkl": 1.0}}
+# name -> (option that keeps the call on the lean family, workload, overrides)
+C4 = {"ntime": 1000, "initialcondition": "diagonal, 0, 1"}
+PEN = {"optim_penalty": 0.1, "optim_penalty_energy": 0.1}
+LEAN_PROBES = {"c4lean": ("sens_lean", "c4", C4), "c4jlean": ("sens_lean", "c4", {**C4, "Jkl": 1.0}),
+               "q4slot": ("sens_slot", "q4", PEN), "c5slot": ("sens_slot", "c5", PEN), "q4jslot": ("sens_slot", "q4j", PEN)}
 
 
 def lean_probe(which):
     from quandary_amd.workloads import workload_spec
 
-    def open_handle(sens_lean):
-        sp = workload_spec("c4", "gradient", {"ntime": 1000, "initialcondition": "diagonal, 0, 1", **LEAN_PROBES[which]})
-        sp.options = {"sens_lean": sens_lean}
+    key, workload, overrides = LEAN_PROBES[which]
+
+    def open_handle(on):
+        sp = workload_spec(workload, "gradient", overrides)
+        sp.options = {key: on}
         h = capi.Handle(sp)
         return sp, h, capi.Optim(h, sp)
 
@@ -62,11 +72,11 @@ def lean_probe(which):
     col = lambda tag, i: [v[i] for v in t[tag]]
     spread = lambda v: max(v) / min(v) - 1.0
     fmt = lambda v: " ".join("%.3f" % x for x in v)
-    print(which, "form ninit", sp.ninit, "ntime", sp.time.ntime, "adjoint_ms plain", fmt(col("plain", 0)), "sens_lean=1", fmt(col("lean", 0)),
+    print(which, "form ninit", sp.ninit, "ntime", sp.time.ntime, "adjoint_ms plain", fmt(col("plain", 0)), key + "=1", fmt(col("lean", 0)),
           "sens_over_plain %.3f" % (min(col("lean", 0)) / min(col("plain", 0))), "spread plain %.3f sens %.3f" % (spread(col("plain", 0)), spread(col("lean", 0))),
           kern["plain"], kern["lean"], flush=True)
     for i, what in ((1, "fwd+adj_ms"), (2, "wall_ms")):
-        print(which, "call ninit", sp.ninit, "ntime", sp.time.ntime, what, "sens_lean=1", fmt(col("lean", i)), "sens_lean=0", fmt(col("general", i)),
+        print(which, "call ninit", sp.ninit, "ntime", sp.time.ntime, what, key + "=1", fmt(col("lean", i)), key + "=0", fmt(col("general", i)),
               "general_over_lean %.3f" % (min(col("general", i)) / min(col("lean", i))), "spread lean %.3f general %.3f" % (spread(col("lean", i)), spread(col("general", i))),
               kern["lean"], kern["general"], flush=True)
     for o, h in ((ol, hl), (og, hg)):

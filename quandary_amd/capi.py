@@ -680,7 +680,8 @@ class Optim:
         """qd_optim_evalGradF_model: (dict, grad, {"transfreq": [nosc], "selfkerr": [nosc], "crosskerr": [npairs]}) - the objective and
         gradient of evalGradF(alpha) and d objective / d constant of the standard model per GHz of the system's field, pairs in the
         system's order, from one forward and one adjoint sweep (k_forward / k_adjoint_sens on the general kernel family; with option
-        sens_lean = 1 the 3x20 class stays on the lean column kernels, k_forward_col / k_adjoint_col_sens).  The function
+        sens_lean = 1 the 3x20 class stays on the lean column kernels, k_forward_col / k_adjoint_col_sens; with option sens_slot = 1
+        the 2^4 / 2^5 Lindblad systems stay on the fp64 lean slot kernels, k_forward_q32 / k_adjoint_q32_sens).  The function
         differentiated is the one evalF_ensemble_model samples.  A name missing from `want` is passed as NULL and comes back as None."""
         alpha = np.ascontiguousarray(alpha, dtype=np.float64)
         val = qd_objective_value()

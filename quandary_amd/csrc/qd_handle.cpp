@@ -1203,7 +1203,7 @@ int qd_handle::prepare_sweep(SweepArgs& a, const SweepPlan& p, int nb, const Dev
     return fail(QD_ERR_UNSUPPORTED, "fp32-mixed sweeps of a system with dipole-dipole coupling: the Krylov kernels are not built (option gmres_split = 0); linearsolver_type = gmres is served by the stationary iteration where it contracts");
   // (the sensitivity form reads the stored stages: none under explicit Euler)
   if (p.form == Form::Sens && (!p.form_built(opts) || sets || S.dense || sol.stepper == QD_STEPPER_EE || !ztraj_doubles(nb)))
-    return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state - and, with option sens_lean, the diagonal-split stationary iteration of the lean column family - sweeps them (standard model, implicit-midpoint family, one control vector)");
+    return fail(QD_ERR_STATE, "model-constant sensitivities: only the general kernel family with one workgroup per state - and, with option sens_lean, the diagonal-split stationary iteration of the lean column family, with option sens_slot the fp64 stationary iterations of the lean slot family - sweeps them (standard model, implicit-midpoint family, one control vector)");
   return QD_OK;
 }
 
@@ -1248,7 +1248,7 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
   typedef hipError_t (*col_fn)(const SweepArgs&, bool, hipStream_t);
   // index Form: Plain, Sets, Vars, Sens
   static const slot_fn f32[4] = {launch_sweep_f32, launch_sweep_f32_sets, launch_sweep_f32_vars, nullptr};
-  static const slot_fn slot[4] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, nullptr};
+  static const slot_fn slot[4] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, launch_sweep_lean64_sens};
   static const col_fn col[4] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, launch_sweep_col_sens};
   const int f = (int)plan.form;
   switch (plan.family) {

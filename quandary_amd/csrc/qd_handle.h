@@ -128,7 +128,9 @@ struct SweepPlan {
   //   or a gmres request served by the Neumann stand-in; their Krylov kernels have no variants form);
   // Sens: the general family (k_adjoint_sens) and, under option sens_lean, the diagonal-split stationary iteration of the lean column
   //   family (k_adjoint_col_sens / k_adjoint_colj_sens: a neumann request, or a gmres request served by that iteration; their Krylov
-  //   and plain-Neumann kernels have no sensitivity form).
+  //   and plain-Neumann kernels have no sensitivity form); under option sens_slot the fp64 lean slot family where the kernel's solver is
+  //   a stationary iteration (k_adjoint_q32_sens: a neumann request or a gmres request served by the stand-in; no Krylov and no
+  //   fp32-mixed kernel has the form).
   bool form_built(const TuneOpts& o) const {
     const bool slot = family == Family::Slot || family == Family::F32, stationary = cfg.gmres == 0;
     switch (form) {
@@ -137,7 +139,9 @@ struct SweepPlan {
       case Form::Vars:
         return (family == Family::Col && stationary && neumann_split) || (family == Family::General && o.ensemble_general) ||
                (o.ensemble_lean && slot && stationary);
-      case Form::Sens: return family == Family::General || (o.sens_lean && family == Family::Col && stationary && neumann_split);
+      case Form::Sens:
+        return family == Family::General || (o.sens_lean && family == Family::Col && stationary && neumann_split) ||
+               (o.sens_slot && family == Family::Slot && stationary);
     }
     return false;
   }
@@ -321,7 +325,8 @@ struct qd_handle {
   int variants_upload(int nvar, const double* blocks, const double* alpha);  // d_vconst, vars_host and vars_bound (at the control vector alpha)
   // Model-constant sensitivities (qd_optim_evalGradF_model): while sens is set the adjoint sweep runs on the sensitivity form of the
   // general family (k_adjoint_sens, qd_sens.h) or, under option sens_lean, of the lean column family (k_adjoint_col_sens /
-  // k_adjoint_colj_sens, qd_col.h) - any other plan is an error - and leaves the sums over the states of
+  // k_adjoint_colj_sens, qd_col.h), under option sens_slot of the lean slot family (k_adjoint_q32_sens, qd_q32.hip) - any other plan is
+  // an error - and leaves the sums over the states of
   // kbar^T (dM/d theta) z in d_senssum [2 Q + npairs]: detunings, self-Kerr, cross-Kerr coefficients, in rad/ns and without the factors
   // -1/2 and -1 of the Kerr terms (the caller applies them with the unit).  d_sens: the sums the kernel stores, one row per state
   // (lean column family: per state and time slice).

@@ -182,6 +182,8 @@ struct TuneOpts {
                            // variant even where the lean column kernels could share its launches (A/B switch; 0 = share, the default)
   int sens_lean = 0;       // "sens_lean": the model-constant sensitivities (qd_optim_evalGradF_model) stay on the lean column kernels where the adjoint plan is
                            // their diagonal-split stationary iteration (k_adjoint_col_sens / k_adjoint_colj_sens; 0 = the general family everywhere, the default)
+  int sens_slot = 0;       // "sens_slot": ... and on the lean slot kernels where the plan is fp64 and its kernel solver a stationary iteration
+                           // (k_adjoint_q32_sens; 0 = the general family there, the default - also under sens_lean, which names the column family alone)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
   double sched_wait_s = 0.0;    // "sched_wait_s": seconds a time slice may wait for its predecessor (0 = automatic: 4 s x the processes that share the
                                 // device (QD_DEVICE_SHARERS, set by the launchers that put several ranks on one GPU) x the slice length in units of 1000 steps)
@@ -290,6 +292,11 @@ hipError_t launch_sweep_lean64_sets(const SweepArgs& a, bool adjoint, const Tune
 // request or a missing table is an error.  Elements per thread of the uncoupled 2^5 system as in the SETS form, from a.nb = variants x states
 hipError_t launch_sweep_f32_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_sweep_lean64_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+// the sensitivity form of the fp64 adjoint sweep (qd_q32.hip compiled with -DQD_SENS=1: k_adjoint_q32_sens, the instantiation
+// launch_sweep_lean64 picks for the same arguments): the stationary iterations only, and the adjoint direction only - a forward or
+// Krylov request, a missing a.S.tred or a.ztraj is an error.  Every state stores its sums of kbar^T (dM/d theta) z to its own row of
+// a.S.tred, [nb][sens_columns(Q)].
+hipError_t launch_sweep_lean64_sens(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
 // lean column kernels (qd_col.hip): Lindblad Neumann sweeps of density matrices with 33..64 rows and runtime level counts
 bool collean_available(const DevSys& S, const TuneOpts& o);

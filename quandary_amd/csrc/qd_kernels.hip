@@ -630,7 +630,7 @@ size_t krylov_doubles(const DevSys& S, int nb) { return (size_t)nb * (GMRES_MR_G
 // options
 // ---------------------------------------------------------------------------------------------
 static const char* const kOptKeys[] = {"var", "force_neumann", "no_mfma", "big_team", "big_spread", "big_blocked", "lean64_sb", "no_lean64", "no_collean",
-                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "batch_lean", "ensemble_loop", "ensemble_general", "ensemble_lean", "sens_lean", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
+                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "batch_lean", "ensemble_loop", "ensemble_general", "ensemble_lean", "sens_lean", "sens_slot", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
 int TuneOpts::set(const char* key, const char* value) {
   if (!key || !value) return -1;
   const std::string k(key), v(value);
@@ -678,6 +678,7 @@ int TuneOpts::set(const char* key, const char* value) {
   else if (k == "ensemble_general") ensemble_general = iv != 0;
   else if (k == "ensemble_lean") ensemble_lean = iv != 0;
   else if (k == "sens_lean") sens_lean = iv != 0;
+  else if (k == "sens_slot") sens_slot = iv != 0;
   else if (k == "col_skip") col_skip = v == "auto" ? 1 : iv != 0;
   else if (k == "no_collean") no_collean = iv != 0;
   else if (k == "no_col_krylov") no_col_krylov = iv != 0;

@@ -1365,7 +1365,9 @@ extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_
 // (k_adjoint_sens): both sweeps are planned there, as options no_collean / no_lean64 would, and the handle is put back afterwards.
 // Under option sens_lean a call whose own plan is the diagonal-split stationary iteration of the lean column family stays on it: the
 // forward sweep as planned, the adjoint sweep on k_adjoint_col_sens / k_adjoint_colj_sens (qd_col.h under QD_COL_SENS), which keeps
-// w = kbar.x z.y - kbar.y z.x summed per element over the sub-steps and applies the integer weights once per task.
+// w = kbar.x z.y - kbar.y z.x summed per element over the sub-steps and applies the integer weights once per task.  Under option
+// sens_slot a call whose own plan is an fp64 stationary iteration of the lean slot family (2^4 / 2^5 Lindblad, with or without Jkl) stays
+// there the same way: forward sweep k_forward_q32, adjoint sweep k_adjoint_q32_sens (qd_q32.hip under QD_SENS), one row of sums per state.
 // ---------------------------------------------------------------------------------------------------------------
 // leaves the handle on its own options, plan latch and tuner state however the call ends
 // latch0: the latch as it was before the caller asked the handle for its own plan (which may have decided it)
@@ -1414,17 +1416,21 @@ extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_obj
   std::vector<double> s(ns);
   // option sens_lean: both sweeps as the handle's own options plan them - where that is the lean column family and the adjoint plan has
   // a sensitivity form (SweepPlan::form_built), the call stays there; anything else takes the general family as without the option
+  // option sens_slot: the same for the lean slot family (2^4 / 2^5 Lindblad in fp64) - the forward sweep the plain k_forward_q32, the
+  // adjoint sweep k_adjoint_q32_sens of the same instantiation (launch_sweep_lean64 / launch_sweep_lean64_sens: one chooser)
   const int latch0 = h->sub_latch;
   bool lean = false;
-  if (h->opts.sens_lean) {
+  Family fam = Family::General;  // the family both sweeps of the call run on
+  if (h->opts.sens_lean || h->opts.sens_slot) {
     if ((r = qd_set_params(h, alpha, h->ndesign))) return r;
     PenaltyScope ps(h, o->pen);
     StagesScope ss(h);
     h->sens = true;  // (the adjoint plan names the form)
     const SweepPlan pf = h->plan_sweep(nl, false), pa = h->plan_sweep(nl, true);
     h->sens = false;
-    lean = pf.family == Family::Col && pa.family == Family::Col && pa.form == Form::Sens && pa.form_built(h->opts);
-    if (!lean) h->sub_latch = latch0;  // (what the gates decided for a plan that is not run is forgotten)
+    lean = (pf.family == Family::Col || pf.family == Family::Slot) && pa.family == pf.family && pa.form == Form::Sens && pa.form_built(h->opts);
+    if (lean) fam = pf.family;
+    else h->sub_latch = latch0;  // (what the gates decided for a plan that is not run is forgotten)
   }
   {
     SensScope scope(h, latch0, !lean);
@@ -1435,8 +1441,8 @@ extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_obj
       const SweepPlan plan = h->plan_sweep(nl, false);
       if (plan.family == Family::Global)
         return fail(QD_ERR_UNSUPPORTED, who + ": the state does not fit one CU's LDS (dim > 4096) - the global-memory kernels have no sensitivity form");
-      if (plan.family != (lean ? Family::Col : Family::General))
-        return fail(QD_ERR_UNSUPPORTED, who + ": the sweep is not planned on a kernel family with a sensitivity form (the general one; with option sens_lean the lean column one)");
+      if (plan.family != fam)
+        return fail(QD_ERR_UNSUPPORTED, who + ": the sweep is not planned on a kernel family with a sensitivity form (the general one; with option sens_lean the lean column one, with option sens_slot the lean slot one)");
       if (!trajectory_fits(h, nl, &o->tg))
         return fail(QD_ERR_UNSUPPORTED, who + ": the stored trajectory of the shard does not fit device memory and would be swept in chunks - not built for the sensitivity form");
     }

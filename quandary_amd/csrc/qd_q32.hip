@@ -39,14 +39,30 @@
 // scalar loads) where Q32::init forms the diagonal of the Hamiltonian and keeps J_kl: the source of those constants (QD_Q32_CONSTS) and
 // the kernel name are the only places where this form differs.  g1 / g2 / g1off, level counts and hasJ remain the handle's; a variant
 // whose J of a pair is 0 keeps the coupled kernel with Jc = 0; selfkerr travels in the table and has no term on two levels.
+//
+// With -DQD_SENS=1 (build/qd_q32_sens.o): the sensitivity form of the ADJOINT sweep, k_adjoint_q32_sens, and its launcher - nothing else
+// (model-constant sensitivities, qd_optim_evalGradF_model with option sens_slot).  dM/d theta of a detuning, a self-Kerr or a cross-Kerr
+// coefficient is diagonal and time-independent - with J_kl != 0 too -, so d objective / d theta is a weighted sum over the elements of
+// W[e] = sum over the sub-steps of kbar_e.x z_e.y - kbar_e.y z_e.x, with the integer weights of qd_sens.h.  A thread keeps W of its EPT
+// elements in fp64 registers across the time loop - two fma per element and sub-step where kbar and z are at hand, nothing per constant -
+// and weights, reduces and stores the sens_count(Q) sums once, to the state's own row of SweepArgs::S.tred [nb][sens_count(Q)] (no
+// atomics: the host adds the rows in a fixed order).  Only the adjoint kernel of the fp64 stationary-iteration instantiations is built:
+// no forward kernel - the forward sweep of the call is the plain k_forward_q32 -, no Krylov kernel, no fp32-mixed kernel, no operator
+// application.
 #ifndef QD_SETS
 #define QD_SETS 0
 #endif
 #ifndef QD_VARS
 #define QD_VARS 0
 #endif
+#ifndef QD_SENS
+#define QD_SENS 0
+#endif
 #if QD_SETS && QD_VARS
 #error "QD_SETS and QD_VARS are objects of their own"
+#endif
+#if QD_SENS && (QD_SETS || QD_VARS)
+#error "QD_SENS: a single evaluation - not together with QD_SETS or QD_VARS"
 #endif
 #if QD_VARS
 #include "qd_col_vars.h"
@@ -59,6 +75,9 @@
 #define QD_Q32_FORWARD k_forward_q32_sets
 #define QD_Q32_ADJOINT k_adjoint_q32_sets
 #define QD_Q32_CTL(A) (A.ctl + (size_t)((unsigned)blockIdx.x / (unsigned)A.nb_set) * A.ctl_set)
+#elif QD_SENS
+#define QD_Q32_ADJOINT k_adjoint_q32_sens  // (no forward kernel)
+#define QD_Q32_CTL(A) A.ctl
 #else
 #define QD_Q32_FORWARD k_forward_q32
 #define QD_Q32_ADJOINT k_adjoint_q32
@@ -1204,6 +1223,7 @@ template <> struct ZTraj<double> {
   }
 };
 
+#if !QD_SENS
 // ---------------------------------------------------------------------------------------------
 // forward sweep (TimeStepper::solveODE for every initial condition of the batch)
 // ---------------------------------------------------------------------------------------------
@@ -1298,6 +1318,7 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
     atomicAdd(A.napply, napply);
   }
 }
+#endif  // !QD_SENS
 
 // ---------------------------------------------------------------------------------------------
 // adjoint sweep (TimeStepper::solveAdjointODE + ImplMidpoint::evolveBWD + compute_dRHS_dParams)
@@ -1321,6 +1342,13 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
   const double jbar_pen = A.jbar[ic * 3 + 0];
   const bool pen_on = A.gamma_penalty > 1e-13;
   const bool wj_on = pen_on && A.penalty_param > 1e-13;
+#if QD_SENS
+  // W of the thread's elements over the sub-steps (the sensitivity form, see the top of the file)
+  static_assert(sizeof(R) == 8 && !GM, "the sensitivity form: fp64 stationary iterations only");
+  double wacc[EPT];
+#pragma unroll
+  for (int j = 0; j < EPT; j++) wacc[j] = 0.0;
+#endif
 
   vm_drain();
   for (int s = A.nsub - 1; s >= 0; s--) {
@@ -1369,6 +1397,11 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
 #pragma unroll
     for (int i = 0; i < 2 * Q; i++) cf[i] = 0.0;
     tm.st.ladder_all(tm.vec(), z, kb, cf);
+#if QD_SENS
+    // kbar^T (dM/d theta) z of the diagonal model operators, before the weights: kbar (h-scaled) and z of the sub-step, both in registers
+#pragma unroll
+    for (int j = 0; j < EPT; j++) wacc[j] = fma(kb[j].x, z[j].y, fma(-kb[j].y, z[j].x, wacc[j]));
+#endif
     auto coeff_dst = [&](int g) -> double* { return A.coeff + ((size_t)ic * A.nsub + s) * 2 * Q + g; };
     tm.template sum_store_post<2 * Q>(cf, coeff_dst);
     // xbar += M^T kbar
@@ -1391,9 +1424,27 @@ __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (QD_F32HJ_W > 0 && HJ && 
       d0[DIM + tm.elem(j)] = xb[j].y;
     }
   }
+#if QD_SENS
+  {  // once per state: the integer weights of the thread's elements from the level digits of their natural index - the index xbarT is
+     // read with - in the oscillator and pair order of qd_sens.h, the workgroup totals, the state's row
+    constexpr int NS = sens_count(Q);
+    double sacc[NS];
+#pragma unroll
+    for (int i = 0; i < NS; i++) sacc[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+      unsigned bra = 0, ket = 0;
+      sens_decode<Q, true>(S, tm.elem(j), bra, ket);
+      sens_add<Q, true>(bra, ket, wacc[j], sacc);
+    }
+#pragma unroll
+    for (int k = 0; k < Q; k++) sacc[Q + k] = 0.0;  // (two levels have no self-Kerr term: exactly zero, whatever W holds)
+    sens_store<NS>(tm, sacc, A.S.tred + (size_t)ic * NS);
+  }
+#endif
 }
 
-#if !QD_SETS && !QD_VARS
+#if !QD_SETS && !QD_VARS && !QD_SENS
 // single operator application (test hook: qd_apply_rhs with QD_PRECISION_F32MIXED; timing loop of the MFMA measurement)
 template <int Q, int SB, typename R, bool HJ = false>
 __global__ void __launch_bounds__((Q32<Q, SB, R>::NT), (Q32<Q, SB, R>::MINW >> (HJ ? 1 : 0))) k_apply_q32(const DevSys S, const double* __restrict__ ctlrow, int transpose,
@@ -1544,7 +1595,7 @@ __global__ void __launch_bounds__(64) k_apply_mfma32(const DevSys S, const doubl
   }
 }
 
-#endif  // !QD_SETS && !QD_VARS
+#endif  // !QD_SETS && !QD_VARS && !QD_SENS
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -1560,14 +1611,23 @@ static hipError_t go_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   const size_t lds = Team32<Q, SB, R, GM, HJ>::lds_bytes();
   // (the forward kernel named first: the compiler emits the kernels in the order they are first named, and its code for two of them
   //  has been seen to depend on that order - profiles/HISTORY.md, "One launcher for both directions")
+#if QD_SENS
+  // (the sensitivity form has no forward kernel - the forward sweep of its call is the plain one: an error, and nothing instantiated)
+  if (!adjoint) return hipErrorInvalidValue;
+  auto kf = QD_Q32_ADJOINT<Q, SB, R, GM, HJ>;
+  hipError_t e = set_lds(kf, lds);
+  if (e != hipSuccess) return e;
+  note_kernel(1, QD_Q32_STR(QD_Q32_ADJOINT), Q, SB, type_name<R>(), GM, HJ);
+#else
   auto kf = !adjoint ? QD_Q32_FORWARD<Q, SB, R, GM, HJ> : QD_Q32_ADJOINT<Q, SB, R, GM, HJ>;
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
   note_kernel(adjoint ? 1 : 0, adjoint ? QD_Q32_STR(QD_Q32_ADJOINT) : QD_Q32_STR(QD_Q32_FORWARD), Q, SB, type_name<R>(), GM, HJ);
+#endif
   hipLaunchKernelGGL(kf, dim3(a.nb), dim3(nt), lds, st, a);
   return hipGetLastError();
 }
-#if !QD_SETS && !QD_VARS
+#if !QD_SETS && !QD_VARS && !QD_SENS
 template <int Q, int SB, typename R, bool HJ = false>
 static hipError_t go_app(const DevSys& S, const double* ctlrow, int tr, const double* x, double* y, int nb, int nrep, hipStream_t st) {
   constexpr int nt = Q32<Q, SB, R>::NT;
@@ -1599,7 +1659,12 @@ static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
 // a.nb / a.nb_set sets, each reading its own control table.  Vars (model-parameter ensemble): the same axis, one control table, the
 // constants table in a.S.hcr - a dense handle or a missing table is an error.  Neither form has Krylov kernels (the degree tuner keeps
 // statistics per handle that a launch of mixed sets would blur): a request for one is an error, never another kernel.
-#if QD_VARS
+// Sens (model-constant sensitivities): the adjoint sweep of a single evaluation on a stationary iteration, with the stored stages and the
+// buffer of the sums - a forward (go_sweep), Krylov or explicit-Euler request, a missing S.tred or ztraj is an error, never another kernel.
+#if QD_SENS
+#define QD_Q32_ENTRY(name) name##_sens
+static bool form_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && a.S.tred && a.ztraj; }
+#elif QD_VARS
 #define QD_Q32_ENTRY(name) name##_vars
 static bool form_args_ok(const SweepArgs& a) {
   return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0 && !a.S.dense && col_vars_tab(a) != nullptr && a.S.npairs == a.S.Q * (a.S.Q - 1) / 2;
@@ -1612,7 +1677,7 @@ static bool form_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >
 static bool form_args_ok(const SweepArgs&) { return true; }
 #endif
 // the Krylov instantiations (GM = true): compiled in the plain unit only
-#if QD_SETS || QD_VARS
+#if QD_SETS || QD_VARS || QD_SENS
 #define QD_Q32_KRYLOV(...)
 #else
 #define QD_Q32_KRYLOV(...) __VA_ARGS__
@@ -1621,6 +1686,7 @@ static bool form_args_ok(const SweepArgs&) { return true; }
 // The instantiation <Q, SB, R, GM, HJ> of a sweep, one chooser per precision for every form.  Stationary iterations: the uncoupled 2^5
 // system picks one or two elements per thread (lean64_sb); the Krylov kernels keep their basis in global memory (fp32: as float2,
 // Hessenberg problem in fp64).  (The order of the lines is the order in which the unit names its kernels: see go_sweep.)
+#if !QD_SENS  // (the sensitivity form is an fp64 kernel: no fp32-mixed chooser)
 hipError_t QD_Q32_ENTRY(launch_sweep_f32)(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
   if (!form_args_ok(a)) return hipErrorInvalidValue;
   if (a.S.hasJ) {  // [r6] dipole-dipole coupling: the coupled stencils in fp32 (stationary iterations only)
@@ -1640,7 +1706,8 @@ hipError_t QD_Q32_ENTRY(launch_sweep_f32)(const SweepArgs& a, bool adjoint, cons
   if (a.S.Q == 3) return go_sweep<3, 0, float>(a, adjoint, st);  // [r3] 2x2x2 (BASELINE config 2): one wave per initial condition
   return hipErrorInvalidValue;
 }
-#if !QD_SETS && !QD_VARS  // (here, between the two choosers: the place of its kernels in the order the unit names them)
+#endif  // !QD_SENS
+#if !QD_SETS && !QD_VARS && !QD_SENS  // (here, between the two choosers: the place of its kernels in the order the unit names them)
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
                             hipStream_t st) {
   if (mfma) {
@@ -1664,6 +1731,7 @@ hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose
 // 4-qubit open system: forward sweep 2.70 -> 2.46 ms against the general kernel, gradient evaluation equal; [r5] two waves of two
 // elements instead of four waves of one: 2.55 against 2.25 ms, not kept).  ([r6] the Krylov solver of these kernels - Team32::kry1 in
 // front of the plain GMRES - also on the coupled stencils.)  lean64_available admits Q = 4 | 5 only.
+// (QD_SENS: launch_sweep_lean64_sens - k_adjoint_q32_sens of the instantiation picked here, one of the five stationary ones.)
 hipError_t QD_Q32_ENTRY(launch_sweep_lean64)(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
   if (!form_args_ok(a) || (a.S.Q != 4 && a.S.Q != 5)) return hipErrorInvalidValue;
   if (a.S.Q == 4 && a.S.hasJ) {
@@ -1683,7 +1751,7 @@ hipError_t QD_Q32_ENTRY(launch_sweep_lean64)(const SweepArgs& a, bool adjoint, c
   return go_sweep<5, 2, double>(a, adjoint, st);
 }
 
-#if !QD_SETS && !QD_VARS
+#if !QD_SETS && !QD_VARS && !QD_SENS
 bool lean64_available(const DevSys& S, const TuneOpts& o) {
   // (dipole-dipole coupling [r5]: instantiations of their own - 2^4 one element per thread, 2^5 two; stationary iterations only)
   if (!S.lindblad || S.dense || (S.Q != 5 && S.Q != 4)) return false;
@@ -1697,6 +1765,6 @@ hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transp
   if (S.Q == 4) return go_app<4, 0, double>(S, ctlrow, transpose, x, y, nb, 1, st);
   return go_app<5, 2, double>(S, ctlrow, transpose, x, y, nb, 1, st);
 }
-#endif  // !QD_SETS && !QD_VARS
+#endif  // !QD_SETS && !QD_VARS && !QD_SENS
 
 }  // namespace qd
