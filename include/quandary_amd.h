@@ -350,6 +350,13 @@ int qd_optim_evalGradF(qd_optim* o, const double* alpha, qd_objective_value* val
  * reversed in this many batches of initial conditions (the storage problem of src/timestepper.cpp:38-48 at 288 GB) - in one pass
  * (forward + adjoint per chunk) wherever the adjoint seeds do not depend on the reduced cost, i.e. everywhere but Schroedinger + Jtrace. */
 int qd_optim_last_chunks(const qd_optim* o);
+/* 1 where the last forward sweep of the local shard (forward_local, evalF, evalF_dist) propagated its initial conditions as Hermitian
+ * pairs rho_2p + i rho_2p+1 (option pair_hermitian), else 0.  qd_last_mean_applies then counts per propagated pair and time step. */
+int qd_optim_last_paired(const qd_optim* o);
+/* Per local initial condition, from the last forward sweep of the whole local shard: the in-loop penalty integral, penalty [nlocal], and
+ * (J_re, J_im, fidelity_re, fidelity_im), out4 [nlocal][4] - what the seven partial sums weigh and add.  Either pointer may be null.
+ * QD_ERR_STATE where no such sweep is at hand. */
+int qd_optim_last_local_results(const qd_optim* o, double* penalty, double* out4);
 
 /* OptimProblem::evalF / evalGradF (src/optimproblem.cpp:224-538) at nset control vectors at once: the trial steps of a line search,
  * the starts of a multi-start optimisation, finite-difference probes, amplitude scans.  alphas [nset][ndesign]; vals [nset];
@@ -549,7 +556,11 @@ int qd_set_precision(qd_handle* h, int precision);
  * fp32-mixed families; 0 = default), ensemble_loop (a model-parameter
  * ensemble goes variant by variant even where it could share launches: see qd_optim_evalF_ensemble_model; 0 = default), sens_lean (qd_optim_evalGradF_model
  * stays on the lean column kernels where their sensitivity form is built: see there; 0 = default), sens_slot (... and on the fp64 lean
- * slot kernels; 0 = default).  Every key is also read from the
+ * slot kernels; 0 = default), pair_hermitian (forward sweeps that store nothing - qd_optim_evalF, qd_optim_evalF_dist,
+ * qd_optim_forward_local without storage - propagate exactly Hermitian Lindblad initial conditions two at a time as rho_a + i rho_b
+ * where the plan is the lean column family's stationary solver serving a neumann request under the absolute rule and the in-loop
+ * penalty, if any, reads the diagonal only (weighted Jmeasure, leakage): auto = shards of more states than the device has compute
+ * units, 1 = wherever those conditions hold, 0 = never; see qd_optim_last_paired).  Every key is also read from the
  * environment variable QD_<KEY> once, at qd_create (tests, measurements).  Unknown keys: QD_ERR_INVALID. */
 int qd_set_option(qd_handle* h, const char* key, const char* value);
 int qd_get_precision(const qd_handle* h);

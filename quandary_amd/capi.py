@@ -182,6 +182,7 @@ EXPORTS = [
     "qd_optim_evalF_batch", "qd_optim_evalGradF_batch", "qd_optim_last_batch_sets",
     "qd_optim_evalF_ensemble", "qd_optim_evalGradF_ensemble",
     "qd_optim_evalF_ensemble_model", "qd_optim_evalGradF_ensemble_model", "qd_optim_evalGradF_model",
+    "qd_optim_last_paired", "qd_optim_last_local_results",
 ]
 COMM_ID_BYTES = 128
 PRECISION = {"f64": 0, "f32mixed": 1}
@@ -241,6 +242,8 @@ def load_library(path=None):
     lib.qd_optim_ninit.argtypes = [vp]
     lib.qd_optim_ninit_local.argtypes = [vp]
     lib.qd_optim_last_chunks.argtypes = [vp]
+    lib.qd_optim_last_paired.argtypes = [vp]
+    lib.qd_optim_last_local_results.argtypes = [vp, c_dp, c_dp]
     lib.qd_optim_initial_state.argtypes = [vp, C.c_int, c_dp, C.POINTER(C.c_int)]
     lib.qd_optim_target_state.argtypes = [vp, C.c_int, c_dp]
     lib.qd_optim_forward_local.argtypes = [vp, c_dp, C.c_int, c_dp]
@@ -562,6 +565,19 @@ class Optim:
     def last_chunks(self):
         """Chunks of the last gradient evaluation (1 = the shard's stored trajectory fitted in HBM)."""
         return self.lib.qd_optim_last_chunks(self._o)
+
+    @property
+    def last_paired(self):
+        """1 where the last forward sweep of the local shard ran on Hermitian pairs (option pair_hermitian)."""
+        return self.lib.qd_optim_last_paired(self._o)
+
+    def last_local_results(self):
+        """Per local initial condition, from the last forward sweep of the whole local shard: (penalty integral [nlocal],
+        (J_re, J_im, fidelity_re, fidelity_im) [nlocal, 4])."""
+        n = self.lib.qd_optim_ninit_local(self._o)
+        pen, out4 = np.zeros(n), np.zeros((n, 4))
+        _check(self.lib, self.lib.qd_optim_last_local_results(self._o, dptr(pen), dptr(out4)), "qd_optim_last_local_results")
+        return pen, out4
 
     # several control vectors in one sweep launch (parameter-set batch): alphas [nset, ndesign]
     def evalF_batch(self, alphas):

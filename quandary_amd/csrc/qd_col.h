@@ -55,6 +55,19 @@
 #if QD_COL_SENS && (QD_COL_SETS || QD_COL_VARS)
 #error "QD_COL_SENS: a single evaluation - not together with QD_COL_SETS or QD_COL_VARS"
 #endif
+// With QD_COL_PAIR 1 (set by qd_col_pair.hip, objects of their own): the pair form of the FORWARD sweep, k_forward_col_pair (forward sweeps
+// on Hermitian pairs, option pair_hermitian).  The Lindblad operator is complex-linear on vec(rho) and maps Hermitian to Hermitian, and
+// so is every step of the stationary solve: state ic of the launch is X = rho_a + i rho_b of two Hermitian initial conditions, and the
+// kernel propagates it like any other state.  The form differs from the plain one in the per-time-step penalty block alone, which sums
+// the two members apart - their diagonals are the real and the imaginary part of X's - and in the two results it writes per state,
+// pen_out[2 ic] and pen_out[2 ic + 1].  Only the forward kernel of the stationary instantiations without coupling is built.  Without
+// the flag this file preprocesses to the text it had before the form existed.
+#ifndef QD_COL_PAIR
+#define QD_COL_PAIR 0
+#endif
+#if QD_COL_PAIR && (QD_COL_SETS || QD_COL_VARS || QD_COL_SENS || QD_COL_HJ)
+#error "QD_COL_PAIR: a single evaluation of a system without coupling - not together with another form"
+#endif
 #if QD_COL_SETS || QD_COL_VARS
 #define QD_COL_CTL(A, ic) (A.ctl + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * A.ctl_set)
 #define QD_COL_GAUGE_TAB(A, ic) (gauge_tab(A) + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * gauge_set(A))
@@ -1403,6 +1416,14 @@ __device__ __forceinline__ int slice_start(const SweepArgs& A, int sl) {
   return (int)((long long)A.ntime * sl / A.nslice) * A.nstages;
 }
 
+// Pair form (QD_COL_PAIR): where the owner of a diagonal element keeps member b's penalty sum - one double per thread behind the column
+// table, the 8 x blockDim.x bytes col_launch adds to the launch.  A second accumulator in registers would live across the pass loop,
+// which has none to spare.
+template <class TM>
+__device__ __forceinline__ double* col_pair_word(unsigned char* smem, int N) {
+  return reinterpret_cast<double*>(smem + TM::ST::tab_off(N) + 48u * (unsigned)TM::ST::ncols(N));
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward sweep (TimeStepper::solveODE for every initial condition of the batch)
 // ---------------------------------------------------------------------------------------------
@@ -1440,7 +1461,11 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
 #pragma unroll
     for (int j = 0; j < EPT; j++) x[j] = tm.st.ok(j) ? make_double2(x0[tm.st.elem(j)], x0[dim + tm.st.elem(j)]) : make_double2(0.0, 0.0);
   }
-  double pen_local = 0.0, pen_uniform = 0.0;
+  double pen_local = 0.0, pen_uniform [[maybe_unused]] = 0.0;  // (no uniform part in the pair form)
+  // (pair form: pen_local sums member a; member b's sum is the thread's word of LDS, touched by the owner of a diagonal element once
+  //  per full time step and addressed where it is used - nothing of it lives across the pass loop)
+  constexpr bool paired = QD_COL_PAIR != 0;
+  if constexpr (paired) col_pair_word<TM>(smem, S.N)[threadIdx.x] = 0.0;
 #if QD_COL_VARS
   // A time-sliced sweep of this form carries every thread's penalty sum from slice to slice (qd_col_vars.h: one block of
   // COL_VARS_PEN_STRIDE doubles per state, the uniform part in its last word) and reduces it once, behind the last slice: the additions
@@ -1530,8 +1555,29 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
       x[j].x = fma(2.0, z[j].x, -x[j].x);
       x[j].y = fma(2.0, z[j].y, -x[j].y);
     }
+    // ... of a Hermitian pair: the weighted Jmeasure and the leakage term read the diagonal, rho_a's in x.x and rho_b's in x.y (a
+    // Hermitian member has a real diagonal, and the frame change leaves the diagonal alone).  The gate admits no other in-loop
+    // penalty and tabulates the weights (A.wjw).
+    if (paired && pen_on && (s + 1) % A.nstages == 0) {  // (paired is a constant of the form)
+      const int n = (s + 1) / A.nstages - 1;
+      const double wrow = wj_on ? kload(A.wjw + n) * A.dt * fabs((double)(tm.st.row - A.tg.purestate_id)) : 0.0;
+#pragma unroll
+      for (int j = 0; j < EPT; j++)
+        if (tm.st.rowok && tm.st.colof(j) == tm.st.row) {
+          double pb = 0.0;
+          if (wj_on) {
+            pen_local = fma(wrow, x[j].x, pen_local);
+            pb = wrow * x[j].y;
+          }
+          if (leak) {
+            pen_local += x[j].x * x[j].x / A.ntime;
+            pb += x[j].y * x[j].y / A.ntime;
+          }
+          col_pair_word<TM>(smem, S.N)[threadIdx.x] += pb;
+        }
+    }
     // in-loop penalties at the end of a FULL time step (timestepper.cpp:141-154, :256-298)
-    if (pen_on && (s + 1) % A.nstages == 0) {
+    if (pen_on && !paired && (s + 1) % A.nstages == 0) {
       const int n = (s + 1) / A.nstages - 1;
       const double tstop = (n + 1) * A.dt;
       if (wj_on) {
@@ -1601,11 +1647,23 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
 #else
   double v[1] = {pen_local};
   tm.template sum<1>(v);
+#if QD_COL_PAIR
+  // the members' sums apart (an odd batch has no second member in its last pair: A.paired = the number of members)
+  double vb[1] = {col_pair_word<TM>(smem, S.N)[threadIdx.x]};
+  tm.template sum<1>(vb);
+  if (threadIdx.x == 0) {
+    A.pen_out[2 * ic] = (sl > 0 ? A.pen_out[2 * ic] : 0.0) + v[0];
+    if (2 * ic + 1 < A.paired) A.pen_out[2 * ic + 1] = (sl > 0 ? A.pen_out[2 * ic + 1] : 0.0) + vb[0];
+    A.dpdm_out[ic] = 0.0;
+    atomicAdd(A.napply, napply);
+  }
+#else
   if (threadIdx.x == 0) {
     A.pen_out[ic] = (sl > 0 ? A.pen_out[ic] : 0.0) + v[0] + pen_uniform;  // (slices of one initial condition run one after the other)
     A.dpdm_out[ic] = 0.0;  // the dpdm penalty is Schroedinger only (timestepper.cpp:143-146)
     atomicAdd(A.napply, napply);
   }
+#endif
 #endif
   if (A.sched) sched_done(A.sched, ic, (unsigned)(sl + 1), tm.lastn);
   }
@@ -1865,8 +1923,14 @@ template <int Q, int EPT, bool SPLIT, bool USLOT, bool SKIP, bool KRY>
 static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
   const int threads = 64 * (ST::ncols(a.S.N) / EPT);
-  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0);
-#if QD_COL_SENS
+  // (pair form: member b's penalty word per thread, col_pair_word; pairs are an error in every other form, and the other way round)
+  if ((a.paired != 0) != (QD_COL_PAIR != 0)) return hipErrorInvalidValue;
+  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0) + (QD_COL_PAIR ? sizeof(double) * (size_t)threads : 0);
+#if QD_COL_PAIR
+  // (the pair form has no adjoint kernel: an error, and nothing instantiated)
+  if (adjoint) return hipErrorInvalidValue;
+  auto kf = QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
+#elif QD_COL_SENS
   // (the sensitivity form has no forward kernel - the forward sweep of its call is the plain one: an error, and nothing instantiated)
   if (!adjoint) return hipErrorInvalidValue;
   auto kf = QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
@@ -1905,7 +1969,7 @@ static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
     return skip ? go(yes, yes, no) : go(yes, no, no);
   }
 #else
-  if constexpr (QD_COL_SETS) {  // (no SETS form of the Krylov kernels: an error, and nothing instantiated)
+  if constexpr (QD_COL_SETS || QD_COL_PAIR) {  // (no SETS or pair form of the Krylov kernels: an error, and nothing instantiated)
     if (a.use_gmres) return hipErrorInvalidValue;
   } else {
     if (a.use_gmres) return go(yes, no, yes);
@@ -1957,8 +2021,16 @@ static bool col_sens_args_ok(const SweepArgs& a, bool adjoint) {
   return adjoint && !a.use_gmres && a.neumann_split && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && a.S.tred && a.ztraj;
 }
 #endif
-#if QD_COL_SETS || QD_COL_VARS || QD_COL_SENS
-#if !QD_COL_SENS
+#if QD_COL_PAIR
+// The units of the pair form: the forward sweep of a single evaluation on the stationary solvers, on a.nb = ceil(a.paired / 2) pairs.
+// Anything else is an error, never another kernel.
+static bool col_pair_args_ok(const SweepArgs& a, bool adjoint) {
+  return !adjoint && !a.use_gmres && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && !a.S.hasJ && a.paired >= 2 && a.nb == (a.paired + 1) / 2 &&
+         !a.traj && !a.ztraj && (!(a.gamma_penalty > 1e-13 && a.penalty_param > 1e-13) || (a.wjw && a.tg.objective_type == QD_OBJ_JMEASURE));
+}
+#endif
+#if QD_COL_SETS || QD_COL_VARS || QD_COL_SENS || QD_COL_PAIR
+#if !QD_COL_SENS && !QD_COL_PAIR
 // The SETS units (and the units of the third form, QD_COL_VARS: a set is a variant): a.nb states = a.nb / a.nb_set sets, each reading its
 // own control table.  A request they cannot serve - the Krylov solver, states that do not divide into sets - is an error, never another
 // kernel.

@@ -1246,10 +1246,10 @@ int qd_handle::arm_slices(qd::SweepArgs& a, int nb, int which) {
 static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool adjoint, const TuneOpts& opts, hipStream_t st) {
   typedef hipError_t (*slot_fn)(const SweepArgs&, bool, const TuneOpts&, hipStream_t);
   typedef hipError_t (*col_fn)(const SweepArgs&, bool, hipStream_t);
-  // index Form: Plain, Sets, Vars, Sens
-  static const slot_fn f32[4] = {launch_sweep_f32, launch_sweep_f32_sets, launch_sweep_f32_vars, nullptr};
-  static const slot_fn slot[4] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, launch_sweep_lean64_sens};
-  static const col_fn col[4] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, launch_sweep_col_sens};
+  // index Form: Plain, Sets, Vars, Sens, Pair
+  static const slot_fn f32[5] = {launch_sweep_f32, launch_sweep_f32_sets, launch_sweep_f32_vars, nullptr, nullptr};
+  static const slot_fn slot[5] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, launch_sweep_lean64_sens, nullptr};
+  static const col_fn col[5] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, launch_sweep_col_sens, launch_sweep_col_pair};
   const int f = (int)plan.form;
   switch (plan.family) {
     case Family::F32: return f32[f] ? f32[f](a, adjoint, opts, st) : hipErrorInvalidValue;
@@ -1259,14 +1259,26 @@ static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool a
   }
 }
 
-int qd_handle::forward_dev(const double* dx0, int nb, bool store, const DevTarget* tgp, double* energy) {
+int qd_handle::forward_dev(const double* dx0, int nb, bool store, const DevTarget* tgp, double* energy, const double* dxpair) {
   int r;
-  if ((r = forward_launch(dx0, nb, store, tgp))) return r;
+  if ((r = forward_launch(dx0, nb, store, tgp, dxpair))) return r;
   return forward_finish(energy);
 }
 
+bool qd_handle::pair_gate(const SweepPlan& plan, int nb, bool store, const DevTarget* tgp) const {
+  if (opts.pair_hermitian == 0 || store || sets || sens || !S.lindblad || S.hasJ || S.dense || nb < 2) return false;
+  // (auto: a shard of at most one state per CU - counted before pairing - has a CU for every state, and pairing shortens nothing)
+  if (opts.pair_hermitian < 0 && nb <= cu_count()) return false;
+  if (plan.family != Family::Col || plan.form != Form::Plain || plan.solver != QD_SOLVER_NEUMANN || plan.cfg.gmres) return false;
+  if (!((float)(sol.reltol * sol.reltol) < 1e-30f)) return false;  // (the relative rule would see ||b|| of the pair)
+  if (pen.gamma_penalty > 1e-13 && pen.penalty_param > 1e-13) {   // weighted penalty: Jmeasure reads the diagonal, the others do not
+    if (!tgp || tgp->objective_type != QD_OBJ_JMEASURE || wjw_param != pen.penalty_param || !d_wjw.p) return false;
+  }
+  return true;
+}
+
 // enqueue the whole forward sweep (tables, kernel, objective pieces, asynchronous result download) on the handle's stream
-int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTarget* tgp) {
+int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTarget* tgp, const double* dxpair) {
   QD_HIP(qd::use_device(device));
   int r;
   if (pen.gamma_penalty > 1e-13 && pen.penalty_param > 1e-13 && !tgp)
@@ -1280,7 +1292,17 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   napply_zeroed = false;
   if (!sets && (r = refresh_tables())) return r;  // (a parameter-set batch has its tables from batch_begin)
   traj_valid = false;
-  const SweepPlan plan = plan_sweep(sets ? nb / sets : nb, false);
+  if ((r = ensure_wj_weights())) return r;
+  SweepPlan plan = plan_sweep(sets ? nb / sets : nb, false);
+  bool paired = false;
+  if (dxpair && !sets) {  // Hermitian pairs: the sweep's plan is the one of the paired count
+    const SweepPlan pp = plan_sweep((nb + 1) / 2, false);
+    if ((paired = pair_gate(pp, nb, store, tgp))) {
+      plan = pp;
+      plan.form = Form::Pair;
+    }
+  }
+  const int nsw = paired ? (nb + 1) / 2 : nb;  // states the kernel propagates
   fwd_poly = plan.gated_poly;
   // (the adjoint sweep's plan differs from this one in the carried-over degree only: the same family)
   const bool full = store && (!stages_only || adjoint_reads_states(nb, tgp, &plan));
@@ -1291,11 +1313,17 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
     if (ztraj_doubles(nb) && (r = d_ztraj.ensure(ztraj_doubles(nb)))) return r;
   }
   if (plan.need_big && (r = ensure_big(nb))) return r;
-  if ((r = ensure_wj_weights())) return r;
   SweepArgs a;
-  if ((r = prepare_sweep(a, plan, nb, tgp))) return r;
+  if ((r = prepare_sweep(a, plan, nsw, tgp))) return r;
   a.x0 = dx0;
   a.xT = d_xT.p;
+  if (paired) {
+    if ((r = d_xpT.ensure((size_t)nsw * 2 * S.dim))) return r;
+    a.x0 = dxpair;
+    a.xT = d_xpT.p;
+    a.paired = nb;
+    QD_HIP(hipMemsetAsync(d_dpdm, 0, sizeof(double) * nb, stream));  // (the kernel writes one word per pair)
+  }
   a.traj = full ? d_traj.p : nullptr;
   a.ztraj = store && ztraj_doubles(nb) ? d_ztraj.p : nullptr;
   a.pen_out = d_pen;
@@ -1305,16 +1333,19 @@ int qd_handle::forward_launch(const double* dx0, int nb, bool store, const DevTa
   QD_HIP(hipEventRecord(ev0, stream));
   if (a.ztraj) ztraj_fmt = plan.stage_layout();
   take_kernel(0);
-  if (plan.family == Family::Col && (r = arm_slices(a, nb, 0))) return r;
+  if (plan.family == Family::Col && (r = arm_slices(a, nsw, 0))) return r;
   if (a.sched && plan.form == Form::Vars) {  // a sliced launch of the variants form carries its penalty sums from slice to slice
     if ((r = d_pencarry.ensure((size_t)nb * COL_VARS_PEN_STRIDE))) return r;
     set_col_vars_pen_carry(a, d_pencarry.p);
   }
   QD_HIP(launch_sweep(a, plan, false, opts, stream));
   last_kernel[0] = take_kernel(0);
+  if (paired) QD_HIP(launch_unpair(S, d_xpT.p, nb, d_xT.p, stream));  // (inside the bracket: last_fwd_ms is the whole of the sweep)
   QD_HIP(hipEventRecord(ev1, stream));
   if (a.sched) QD_HIP(hipMemcpyAsync(h_sched.p, a.sched + 1, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   sliced_fwd = a.sched != nullptr;
+  last_paired = paired;
+  last_solved = nsw;
   if (tgp) QD_HIP(launch_objective(S, *tgp, d_xT.p, nb, d_out4, stream));
   // every result of the sweep in one pinned buffer, one synchronisation
   if ((r = h_res.ensure((size_t)6 * nb + 1))) return r;
@@ -1337,7 +1368,8 @@ int qd_handle::forward_finish(double* energy) {
   float ms = 0.f;
   QD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
   last_fwd_ms = accumulate_fwd_ms ? last_fwd_ms + ms : ms;
-  last_mean_applies = (double)nap / ((double)nb * (double)tg.ntime);  // per TIME step (all stages of a composite step)
+  // per TIME step (all stages of a composite step) of a state the kernel propagated (a Hermitian pair is one)
+  last_mean_applies = (double)nap / ((double)last_solved * (double)tg.ntime);
   // Degree p of the polynomial preconditioner (Team::gmres_g): a solve costs 1 + k p applications plus k rounds of
   // orthogonalisation, reductions and basis traffic (k = Krylov vectors; on the 3x20 workload one such round costs as much as five
   // applications), so the best p is the smallest one for which (almost) every solve needs a single Krylov vector.  k is known after

@@ -94,8 +94,12 @@ enum class Family { General = 0, F32 = 1, Slot = 2, Col = 3, Global = 4 };
 // Form of the sweep kernels, the second axis of the same decision (every family has the plain form, a missing one is an error):
 // Plain: one control vector, one set of model constants; Sets: one control table per parameter set (qd_handle::sets without a constants
 // table); Vars: one block of model constants per ensemble variant and one control table (sets with qd_handle::vars_tab); Sens: the adjoint
-// sweep of a single evaluation that also sums the model-constant sensitivities (qd_handle::sens).
-enum class Form : int { Plain = 0, Sets = 1, Vars = 2, Sens = 3 };
+// sweep of a single evaluation that also sums the model-constant sensitivities (qd_handle::sens); Pair: the forward sweep of a single
+// evaluation on Hermitian pairs (qd_handle::pair_gate turns a plain plan into it; the lean column family alone has the kernels).
+enum class Form : int { Plain = 0, Sets = 1, Vars = 2, Sens = 3, Pair = 4 };
+// the pair form of the lean column forward sweep (qd_col_pair.hip: k_forward_col_pair): a.paired members as a.nb = ceil(a.paired / 2)
+// states; an adjoint sweep, a Krylov request, a coupled system or an in-loop penalty that reads off-diagonal elements is an error
+hipError_t launch_sweep_col_pair(const SweepArgs& a, bool adjoint, hipStream_t st);
 
 // Gershgorin bounds of a row of M for the current parameters (qd_handle::row_bounds) and the largest alpha = |h| / 2 of the step
 // schedule: what every solver gate looks at, computed once per plan
@@ -142,6 +146,7 @@ struct SweepPlan {
       case Form::Sens:
         return family == Family::General || (o.sens_lean && family == Family::Col && stationary && neumann_split) ||
                (o.sens_slot && family == Family::Slot && stationary);
+      case Form::Pair: return family == Family::Col && stationary;
     }
     return false;
   }
@@ -255,11 +260,24 @@ struct qd_handle {
   int traj_doubles(int nb, size_t* n) const;
   size_t ztraj_doubles(int nb) const;  // 0 for explicit Euler
   // forward sweep on device-resident states; results stay on the device (d_pen, d_dpdm, d_xT, d_out4)
-  int forward_dev(const double* dx0, int nb, bool store, const qd::DevTarget* tg, double* energy);
+  // (dxpair: the same states as Hermitian pairs, [(nb + 1) / 2][2 dim] - where the caller knows every state to be exactly Hermitian)
+  int forward_dev(const double* dx0, int nb, bool store, const qd::DevTarget* tg, double* energy, const double* dxpair = nullptr);
   // the same in two halves: enqueue only / synchronise and collect (lets the caller queue the reductions, the adjoint
   // sweep and the collectives behind the forward sweep without a host round trip)
-  int forward_launch(const double* dx0, int nb, bool store, const qd::DevTarget* tg);
+  int forward_launch(const double* dx0, int nb, bool store, const qd::DevTarget* tg, const double* dxpair = nullptr);
   int forward_finish(double* energy);
+  // Hermitian pairs.  M(t) is complex-linear on vec(rho) and maps Hermitian to Hermitian, and so is every step of the lean column
+  // stationary solve: for Hermitian rho_a, rho_b one sweep of X = rho_a + i rho_b carries both, rho_a(t) = (X + X^dagger) / 2 and
+  // rho_b(t) = (X - X^dagger) / 2i.  A forward sweep that stores nothing then runs ceil(nb / 2) tasks on the same kernel, sums the
+  // in-loop penalties of the members apart (qd_col.h) and un-pairs the final states into d_xT, where the objective kernels and every
+  // caller find the nb states they find after an unpaired sweep.  pair_gate: the plan (made for the paired count) and the call admit
+  // it, and the sweep then runs in the form Form::Pair - Lindblad without coupling, one control vector, nothing stored, the plain form of the lean column family with the stationary
+  // solver serving a neumann request under the absolute rule alone (the stopping test then sees ||dX||^2 = ||d rho_a||^2 + ||d rho_b||^2:
+  // each member meets the reference's rule), and no in-loop penalty that reads off-diagonal elements; option pair_hermitian.
+  bool pair_gate(const qd::SweepPlan& plan, int nb, bool store, const qd::DevTarget* tg) const;
+  qd::DBuf d_xpT;            // the propagated pairs: carry between time slices, source of the un-pairing
+  bool last_paired = false;  // the last forward sweep ran on pairs
+  int last_solved = 0;       // states its kernel propagated: last_nb, or (last_nb + 1) / 2 pairs
   int adjoint_launch(const double* dxbarT, const double* djbar, int nb, const qd::DevTarget* tg, bool accumulate);
   int adjoint_finish(bool accumulate);
   int gradient_launch(double ebar, double* dgrad);  // k_grad into a device buffer [ndesign]

@@ -101,6 +101,11 @@ struct SweepArgs {
   // (timestepper.cpp:262-270, :304-315); tabulated once per handle so that the sweep kernels of qd_col.hip need no exp() per step
   const double* wjw;
   int use_gmres;  // 0: Neumann; 1: in-kernel GMRES, Krylov basis in LDS (one element per thread, small dim); 2: basis in global memory (kry)
+  // Hermitian pairs (pair form of the lean column forward sweep, qd_col_pair.hip; qd_handle::pair_gate): 0, or the number nl of Hermitian
+  // initial conditions whose pairs X_p = rho_2p + i rho_2p+1 are the nb = ceil(nl / 2) states of the launch - the penalty block of that
+  // form sums the members of a pair apart, pen_out[2 ic] and pen_out[2 ic + 1].  (In what was padding behind use_gmres: size and
+  // offsets of the struct stay.)
+  int paired;
   double abstol, reltol;
   double inv_abs2;  // 1 / abstol^2 and reltol^2 as the solvers use them: kernel arguments are re-read from the scalar cache, values
   float rel2;       // derived inside the kernel were hoisted out of the time loop and spilt to scratch (one round trip per solve)
@@ -184,6 +189,9 @@ struct TuneOpts {
                            // their diagonal-split stationary iteration (k_adjoint_col_sens / k_adjoint_colj_sens; 0 = the general family everywhere, the default)
   int sens_slot = 0;       // "sens_slot": ... and on the lean slot kernels where the plan is fp64 and its kernel solver a stationary iteration
                            // (k_adjoint_q32_sens; 0 = the general family there, the default - also under sens_lean, which names the column family alone)
+  int pair_hermitian = -1;  // "pair_hermitian": forward sweeps that store nothing propagate exactly Hermitian Lindblad initial conditions two at a time, as
+                            // rho_a + i rho_b, where the plan is the lean column stationary solver (qd_handle::pair_gate; -1 = auto: shards
+                            // of more states than the device has CUs, 0 = never, 1 = wherever the gate admits it)
   double traj_budget_mb = 0.0;  // "traj_budget_mb": pretend the trajectory budget is this small (chunked re-propagation)
   double sched_wait_s = 0.0;    // "sched_wait_s": seconds a time slice may wait for its predecessor (0 = automatic: 4 s x the processes that share the
                                 // device (QD_DEVICE_SHARERS, set by the launchers that put several ranks on one GPU) x the slice length in units of 1000 steps)
@@ -262,6 +270,9 @@ hipError_t launch_ensemble_mean(const double* g, const double* reg, int nreg, co
 hipError_t launch_objective(const DevSys& S, const DevTarget& tg, const double* x, int nb, double* out4, hipStream_t st);
 hipError_t launch_seed(const DevSys& S, const DevTarget& tg, const double* x, const double* rbar_ibar, int nb, double* xbar,
                        hipStream_t st);
+// Hermitian pairs: xp [(nl + 1) / 2][2 dim] = x[2p] + i x[2p + 1] of nl Lindblad states, and the nl members back from the pairs
+hipError_t launch_pair(const DevSys& S, const double* x, int nl, double* xp, hipStream_t st);
+hipError_t launch_unpair(const DevSys& S, const double* xp, int nl, double* x, hipStream_t st);
 hipError_t launch_partial_sums(const double* res, int nb, const double* w, double inv_ninit, const qd_penalty& pen, const double* etable,
                                int cs, int Q, int nstep, double* sums, hipStream_t st);
 hipError_t launch_seed_weights(const double* sums, const double* w, int nb, int objective_type, int lindblad, double* rbib, hipStream_t st);

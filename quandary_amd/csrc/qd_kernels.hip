@@ -630,7 +630,7 @@ size_t krylov_doubles(const DevSys& S, int nb) { return (size_t)nb * (GMRES_MR_G
 // options
 // ---------------------------------------------------------------------------------------------
 static const char* const kOptKeys[] = {"var", "force_neumann", "no_mfma", "big_team", "big_spread", "big_blocked", "lean64_sb", "no_lean64", "no_collean",
-                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "batch_lean", "ensemble_loop", "ensemble_general", "ensemble_lean", "sens_lean", "sens_slot", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart"};
+                                       "col_slices", "no_plain", "col_min_n", "gmres_poly", "gmres_split", "neumann_split", "traj_budget_mb", "batch_lean", "ensemble_loop", "ensemble_general", "ensemble_lean", "sens_lean", "sens_slot", "standin_tau", "sched_wait_s", "col_skip", "no_col_krylov", "krylov_tau", "krylov_restart", "pair_hermitian"};
 int TuneOpts::set(const char* key, const char* value) {
   if (!key || !value) return -1;
   const std::string k(key), v(value);
@@ -689,6 +689,7 @@ int TuneOpts::set(const char* key, const char* value) {
   else if (k == "gmres_poly") gmres_poly = iv > 0 ? (int)iv : 0;
   else if (k == "neumann_split") neumann_split = iv < 0 ? -1 : iv != 0;
   else if (k == "gmres_split") gmres_split = iv < 0 ? -1 : iv != 0;
+  else if (k == "pair_hermitian") pair_hermitian = v == "auto" ? -1 : iv != 0;
   else return -1;
   return 0;
 }
@@ -761,6 +762,7 @@ static bool form_args_ok(Form form, const SweepArgs& a, const LaunchCfg& cfg) {
     case Form::Sets: return sets_axis && (cfg.qubit == 2) == (a.S.dense != 0) && (!a.S.dense || (a.S.gtab && a.gtab_set));
     case Form::Vars: return sets_axis && model && a.S.hcr != nullptr;
     case Form::Sens: return model && a.nb_set == 0 && !a.stepper_ee && a.S.tred && a.ztraj;
+    case Form::Pair: return false;  // (the lean column family alone: qd_col_pair.hip)
   }
   return false;
 }
@@ -858,6 +860,46 @@ hipError_t launch_objective(const DevSys& S, const DevTarget& tg, const double* 
   if (S.lindblad) hipLaunchKernelGGL(k_objective<true>, dim3(nb, P), dim3(256), 0, st, S, tg, x, out4, S.tred);
   else hipLaunchKernelGGL(k_objective<false>, dim3(nb, P), dim3(256), 0, st, S, tg, x, out4, S.tred);
   if (P > 1) hipLaunchKernelGGL(k_objective_sum, dim3(nb), dim3(64), 0, st, S.tred, P, out4);
+  return hipGetLastError();
+}
+
+// Hermitian pairs (qd_handle::pair_gate).  k_pair: X_p = rho_2p + i rho_2p+1 of the nl states x [nl][2 dim] (the last pair of an odd
+// batch has no second member: zero); k_unpair: the nl members back from the (nl + 1) / 2 propagated pairs, rho_a = (X + X^dagger) / 2 and
+// rho_b = (X - X^dagger) / 2i, out of place.  One thread per element (i, j) = e % N, e / N.
+__global__ void __launch_bounds__(256) k_pair(const double* __restrict__ x, int nl, int dim, double* __restrict__ xp) {
+  const int p = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= dim) return;
+  const double* a = x + (size_t)(2 * p) * 2 * dim;
+  const bool hb = 2 * p + 1 < nl;
+  const double* b = a + (hb ? (size_t)2 * dim : 0);
+  const double ub = hb ? b[e] : 0.0, vb = hb ? b[dim + e] : 0.0;
+  double* o = xp + (size_t)p * 2 * dim;
+  o[e] = a[e] - vb;
+  o[dim + e] = a[dim + e] + ub;
+}
+__global__ void __launch_bounds__(256) k_unpair(const double* __restrict__ xp, int nl, int N, double* __restrict__ x) {
+  const int p = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x, dim = N * N;
+  if (e >= dim) return;
+  const int et = (e % N) * N + e / N;  // (j, i)
+  const double* s = xp + (size_t)p * 2 * dim;
+  const double re = s[e], im = s[dim + e], ret = s[et], imt = s[dim + et];
+  double* a = x + (size_t)(2 * p) * 2 * dim;
+  a[e] = 0.5 * (re + ret);
+  a[dim + e] = 0.5 * (im - imt);
+  if (2 * p + 1 < nl) {
+    double* b = a + (size_t)2 * dim;
+    b[e] = 0.5 * (im + imt);
+    b[dim + e] = 0.5 * (ret - re);
+  }
+}
+hipError_t launch_pair(const DevSys& S, const double* x, int nl, double* xp, hipStream_t st) {
+  if (!S.lindblad || nl < 1 || (nl + 1) / 2 > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pair, dim3((S.dim + 255) / 256, (nl + 1) / 2), dim3(256), 0, st, x, nl, S.dim, xp);
+  return hipGetLastError();
+}
+hipError_t launch_unpair(const DevSys& S, const double* xp, int nl, double* x, hipStream_t st) {
+  if (!S.lindblad || nl < 1 || (nl + 1) / 2 > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_unpair, dim3((S.dim + 255) / 256, (nl + 1) / 2), dim3(256), 0, st, xp, nl, S.N, x);
   return hipGetLastError();
 }
 

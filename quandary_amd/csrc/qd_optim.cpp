@@ -30,6 +30,10 @@ struct qd_optim {
   qd_penalty pen{};
   // device-resident batch
   DBuf d_x0, d_tgt, d_pur, d_rbib, d_jbar, d_xbar;
+  // Hermitian pairs (qd_handle::pair_gate): the local initial conditions two by two as rho_2p + i rho_2p+1, built once where every one
+  // of them is exactly Hermitian (nullptr otherwise: the sweeps then never pair)
+  DBuf d_xp;
+  bool last_paired = false;  // qd_optim_last_paired
   DBuf d_w, d_red;   // multi-GPU path: beta_i of the local shard; [7 sums | ndesign gradient] reduced in place by RCCL
   HBuf h_red;
   hipEvent_t evr[4] = {nullptr, nullptr, nullptr, nullptr};  // brackets of the two collectives
@@ -216,6 +220,26 @@ static int prepare_initial_state(const qd_optim* o, int iinit, double* rho0) {
   return id;
 }
 
+// Hermitian pairs: may the local initial conditions be propagated two at a time?  The families that are Hermitian by construction -
+// never a file or an ensemble input - and, checked on the host copy, every state EXACTLY so: u symmetric, v antisymmetric.
+static bool pairable_initial_states(const qd_optim* o, const std::vector<double>& x0) {
+  const DevSys& S = o->h->S;
+  if (!S.lindblad || o->nlocal < 2 || (o->nlocal + 1) / 2 > 65535) return false;  // (the pairs are grid.y of k_pair / k_unpair)
+  switch (o->initcond_type) {
+    case QD_INIT_BASIS: case QD_INIT_DIAGONAL: case QD_INIT_NPLUSONE: case QD_INIT_THREESTATES: case QD_INIT_PERFORMANCE: break;
+    default: return false;
+  }
+  const int N = S.N;
+  const size_t dim = (size_t)S.dim;
+  for (int i = 0; i < o->nlocal; i++) {
+    const double *u = x0.data() + (size_t)i * 2 * dim, *v = u + dim;
+    for (int c = 0; c < N; c++)
+      for (int r = 0; r <= c; r++)
+        if (u[r + (size_t)c * N] != u[c + (size_t)r * N] || v[r + (size_t)c * N] != -v[c + (size_t)r * N]) return false;
+  }
+  return true;
+}
+
 static void fill_from_file(const qd_handle* h, const double* data, std::vector<double>& v) {
   const DevSys& S = h->S;
   const int dim = S.dim, N = S.N, de = h->dim_ess;
@@ -244,7 +268,7 @@ extern "C" void qd_optim_destroy(qd_optim* o) {
   if (!o) return;
   (void)hipSetDevice(o->h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
-  for (DBuf* b : {&o->d_x0, &o->d_tgt, &o->d_pur, &o->d_rbib, &o->d_jbar, &o->d_xbar, &o->d_w, &o->d_red}) b->release();
+  for (DBuf* b : {&o->d_x0, &o->d_tgt, &o->d_pur, &o->d_rbib, &o->d_jbar, &o->d_xbar, &o->d_w, &o->d_red, &o->d_xp}) b->release();
   for (DBuf* b : {&o->d_bx0, &o->d_btgt, &o->d_bpur, &o->d_bjbar, &o->d_brbib, &o->d_bxbar, &o->d_ew, &o->d_ereg, &o->d_emean}) b->release();
   o->h_red.release();
   for (hipEvent_t e : o->evr)
@@ -397,6 +421,11 @@ extern "C" int qd_optim_create(qd_handle* h, const qd_objective* ob, int rank, i
     if ((r = o->d_x0.ensure(x0.size())) || (r = o->d_pur.ensure(o->nlocal))) return r;
     QD_HIP(hipMemcpy(o->d_x0.p, x0.data(), sizeof(double) * x0.size(), hipMemcpyHostToDevice));
     QD_HIP(hipMemcpy(o->d_pur.p, pur.data(), sizeof(double) * o->nlocal, hipMemcpyHostToDevice));
+    if (collean_available(S, h->opts) && pairable_initial_states(o, x0)) {  // (the one kernel family that sweeps pairs)
+      if ((r = o->d_xp.ensure((size_t)((o->nlocal + 1) / 2) * n2))) return r;
+      QD_HIP(launch_pair(S, o->d_x0.p, o->nlocal, o->d_xp.p, h->stream));
+      QD_HIP(hipStreamSynchronize(h->stream));
+    }
     if (need_tgt) {
       if ((r = o->d_tgt.ensure(tgt.size()))) return r;
       QD_HIP(hipMemcpy(o->d_tgt.p, tgt.data(), sizeof(double) * tgt.size(), hipMemcpyHostToDevice));
@@ -593,7 +622,7 @@ static int plan_chunk(qd_handle* h, int nl, const DevTarget* tg) {
   if (lo < 1) return 0;
   const int nchunks = (nl + lo - 1) / lo;
   int chunk = (nl + nchunks - 1) / nchunks;
-  const int round = 256;  // CUs of the device: one workgroup per initial condition and CU on the large systems that get here
+  const int round = cu_count();  // one workgroup per initial condition and CU on the large systems that get here
   const int up = (chunk + round - 1) / round * round;
   if (up <= lo) chunk = up;
   return chunk;
@@ -612,10 +641,12 @@ extern "C" int qd_optim_forward_local(qd_optim* o, const double* alpha, int stor
   double energy = 0.0;
   {
     PenaltyScope ps(h, o->pen);  // the objective's penalty block, for this call only (operator-level calls keep theirs)
-    if ((r = h->forward_dev(o->d_x0.p, nl, store, &o->tg, &energy))) return r;
+    // (a sweep that stores nothing may run on Hermitian pairs: qd_handle::pair_gate)
+    if ((r = h->forward_dev(o->d_x0.p, nl, store, &o->tg, &energy, store_trajectory == 0 ? o->d_xp.p : nullptr))) return r;
   }
   o->stored = store;
   o->forward_done = true;
+  o->last_paired = h->last_paired;
   for (int i = 0; i < QD_NSUMS; i++) partial[i] = 0.0;
   add_partial_sums(o, 0, nl, energy, partial);
   return QD_OK;
@@ -774,6 +805,19 @@ static int gradient_one_pass(qd_optim* o, const double* alpha, double* sums, dou
 static bool seeds_need_global_cost(const qd_optim* o) { return !o->h->S.lindblad && o->objective_type == QD_OBJ_JTRACE; }
 
 extern "C" int qd_optim_last_chunks(const qd_optim* o) { return o ? o->last_chunks : QD_ERR_INVALID; }
+extern "C" int qd_optim_last_paired(const qd_optim* o) { return o ? (o->last_paired ? 1 : 0) : QD_ERR_INVALID; }
+
+// per local initial condition, from the last forward sweep of the WHOLE shard (forward_local, evalF, evalF_dist or the first sweep of a
+// gradient evaluation whose trajectory fits): the in-loop penalty integral [nlocal] and (J_re, J_im, fid_re, fid_im) [nlocal][4]
+extern "C" int qd_optim_last_local_results(const qd_optim* o, double* penalty, double* out4) {
+  if (!o) return fail(QD_ERR_INVALID, "qd_optim_last_local_results: null argument");
+  const qd_handle* h = o->h;
+  if (!o->forward_done || h->last_nb != o->nlocal || !h->h_res.p)
+    return fail(QD_ERR_STATE, "qd_optim_last_local_results: no forward sweep of the whole local shard is at hand");
+  if (penalty) std::copy(h->res_pen(), h->res_pen() + o->nlocal, penalty);
+  if (out4) std::copy(h->res_out4(), h->res_out4() + 4 * (size_t)o->nlocal, out4);
+  return QD_OK;
+}
 
 extern "C" int qd_optim_evalGradF(qd_optim* o, const double* alpha, qd_objective_value* val, double* grad) {
   if (!o || !val || !grad) return fail(QD_ERR_INVALID, "qd_optim_evalGradF: null argument");
@@ -877,7 +921,8 @@ static int dist_forward(qd_optim* o, qd_comm* c, const double* alpha, bool store
   int r;
   if ((r = qd_set_params(h, alpha, h->ndesign))) return r;
   o->last_alpha.assign(alpha, alpha + h->ndesign);
-  if ((r = h->forward_launch(o->d_x0.p, o->nlocal, store, &o->tg))) return r;
+  if ((r = h->forward_launch(o->d_x0.p, o->nlocal, store, &o->tg, store ? nullptr : o->d_xp.p))) return r;
+  o->last_paired = h->last_paired;
   QD_HIP(launch_partial_sums(h->d_res.p, o->nlocal, o->d_w.p, 1.0 / o->ninit, o->pen, h->d_etable.p, h->cs, h->S.Q, h->tg.ntime,
                              o->d_red.p, h->stream));
   o->stored = store;
