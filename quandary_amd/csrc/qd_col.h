@@ -1,74 +1,84 @@
-// qd_col.h - device code of the lean column kernels, shared by their two translation units: qd_col.hip (systems without dipole-dipole
-// coupling: k_*_col) and qd_colj.hip (J_kl != 0: k_*_colj).  Layout and reference semantics: the comment at the top of qd_col.hip.
-// The including unit names its kernels and fixes the coupling flag first:
-//   #define QD_COLK(base) base##_col   /  base##_colj      (k_forward, k_adjoint, k_apply)
-//   #define QD_COL_HJ false            /  true
-// The kernels are defined here, once per unit, as __global__ templates over <Q, EPT, SPLIT, USLOT, SKIP, KRY> / <Q, EPT, SPLIT>: the
-// coupling is part of the kernel's NAME, not a template argument of it.  So are their launchers (the end of this file): which
-// instantiation a sweep runs is written once, for both units and both directions.
+// qd_col.h - device code and launchers of the lean column kernels, shared by every translation unit of the family.  Layout and reference
+// semantics: the comment at the top of qd_col.hip.
+//
+// A unit is this file compiled for one (form, coupling); both come from the compile line and default to the plain unit without coupling:
+//   QD_COL_FORM  a value of qd::Form (QD_FORM_* of qd_internal.h)                                default QD_FORM_PLAIN
+//   QD_COL_HJ    1: systems with dipole-dipole coupling (any J_kl != 0), 0: systems without        default 0
+// The kernels are defined here, once per unit, as __global__ templates over <Q, EPT, SPLIT, USLOT, SKIP, KRY> / <Q, EPT, SPLIT>; form and
+// coupling are part of the kernel's NAME (QD_COLK below), not template arguments of it.  So are their launchers (the end of this file):
+// which instantiation a sweep runs is written once, for every unit and both directions.
+//
+// The units: qd_col.hip and qd_colj.hip are the plain ones, each one object with every <Q, EPT>, the operator application and (qd_col.hip)
+// the family's entry points.  Every other unit is qd_col_form.hip compiled once per <Q, EPT> (objects qd_col_sets_3_5.o, ... - they
+// compile side by side), and a form differs from the plain one in the device code only where an #if on QD_COL_FORM says so; with
+// the plain form this file preprocesses to the text it had before the forms existed.
+//   Sets  k_*_col_sets / k_*_colj_sets: the stationary-iteration sweeps, compiled a second time (16 kernels per object without coupling,
+//         4 with).  The task of initial condition ic reads its step rows from the control table of set ic / SweepArgs::nb_set
+//         (parameter-set batch, qd_optim_evalGradF_batch with option batch_lean), the addressing sweep_ctl<true> of qd_device.h gives the
+//         general kernels: wave-uniform, so the rows stay scalar loads.  Trajectory, primal stages, coefficients, carry buffers and
+//         scheduler words stay indexed by ic.  The table address and the kernel names are the only places where the device code differs;
+//         with coupling, the pair columns cos / sin(eta_kl t) widen a table row, not the addressing.
+//   Vars  k_*_col_vars / k_*_colj_vars: one block of model constants per variant (model-parameter ensemble,
+//         qd_optim_evalGradF_ensemble_model; 8 kernels per object without coupling, 4 with).  The task of initial condition ic belongs to
+//         variant ic / SweepArgs::nb_set: it reads that variant's control and phasor tables as the Sets form does, and its detunings,
+//         Kerr coefficients and couplings from the device table of qd_col_vars.h through the scalar path.  Everything ColLean::init
+//         derives from those constants is derived again, by the same text, when a workgroup's task belongs to another variant than its
+//         previous one (col_vars_enter below).  A variant whose couplings are all zero runs on the coupled unit too, with zero weights.
+//   Sens  k_adjoint_col_sens / k_adjoint_colj_sens: the ADJOINT sweep with the model-constant sensitivities (qd_optim_evalGradF_model
+//         with option sens_lean; 4 kernels per object without coupling, 2 with).  dM/d theta of a detuning, a self-Kerr or a cross-Kerr
+//         coefficient is diagonal and time-independent, so d objective / d theta is a weighted sum over the elements of W[e] = sum over
+//         the sub-steps of kbar_e.x z_e.y - kbar_e.y z_e.x, with the integer weights of qd_sens.h.  A thread keeps W of its EPT elements
+//         in fp64 registers across the time loop - two fma per element and sub-step where kbar and z are at hand, nothing per constant -
+//         and weights, reduces and stores the sens_count(Q) sums once per task, to the task's own row of SweepArgs::S.tred
+//         [nslice][nb][sens_count(Q)] (no atomics: the host adds the rows in a fixed order).  The coupling has no part in dM/d theta: the
+//         coupled unit forms the same sums from its own kbar and z.  The forward sweep of the call is the plain kernel.
+//   Pair  k_forward_col_pair: the FORWARD sweep on Hermitian pairs (option pair_hermitian; 8 kernels per object).  The Lindblad operator
+//         is complex-linear on vec(rho) and maps Hermitian to Hermitian, and so is every step of the stationary solve: state ic of the
+//         launch is X = rho_a + i rho_b of two Hermitian initial conditions, and the kernel propagates it like any other state.  The form
+//         differs from the plain one in the per-time-step penalty block alone, which sums the two members apart - their diagonals are
+//         the real and the imaginary part of X's - and in the two results it writes per state, pen_out[2 ic] and pen_out[2 ic + 1].
+// What is built of each form: the properties below.
 #pragma once
-#if !defined(QD_COLK) || !defined(QD_COL_HJ)
-#error "define QD_COLK and QD_COL_HJ before including qd_col.h"
-#endif
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
+#include "qd_col_vars.h"
 #include "qd_device.h"
 #include "qd_gauge.h"
 
-// With QD_COL_SETS 1 (set by qd_col_sets.hip / qd_colj_sets.hip before the include, objects of their own): the SETS form of the
-// stationary-iteration sweeps, k_*_col_sets / k_*_colj_sets - the same templates, compiled a second time.  The task of initial condition
-// ic reads its step rows from the control table of set ic / SweepArgs::nb_set (parameter-set batch, qd_optim_evalGradF_batch with option
-// batch_lean), the addressing sweep_ctl<true> of qd_device.h gives the general kernels: wave-uniform, so the rows stay scalar loads.
-// Trajectory, primal stages, coefficients, carry buffers and scheduler words stay indexed by ic.  The table address and the kernel names
-// are the only places where the device code of the forms differs; on the host side col_sweep refuses the Krylov solver, which has no
-// SETS form.  Without the flag this file preprocesses to the text it had before the form existed.
-#ifndef QD_COL_SETS
-#define QD_COL_SETS 0
+#ifndef QD_COL_FORM
+#define QD_COL_FORM QD_FORM_PLAIN
 #endif
-// With QD_COL_VARS 1 (set by qd_col_vars.hip / qd_colj_vars.hip, objects of their own): the third form, k_*_col_vars / k_*_colj_vars - one
-// block of model constants per variant (model-parameter ensemble, qd_optim_evalGradF_ensemble_model).  The task of initial condition ic
-// belongs to variant ic / SweepArgs::nb_set: it reads that variant's control and phasor tables as the SETS form does, and its detunings,
-// Kerr coefficients and couplings from the device table of qd_col_vars.h through the scalar path.  Everything ColLean::init derives from
-// those constants is derived again, by the same text, when a workgroup's task belongs to another variant than its previous one
-// (col_vars_enter below).  Only the diagonal-split stationary instantiations are built.
-#ifndef QD_COL_VARS
-#define QD_COL_VARS 0
+#ifndef QD_COL_HJ
+#define QD_COL_HJ 0
 #endif
-#if QD_COL_VARS
-#include "qd_col_vars.h"
+// A kernel of the unit: QD_COLK(k_forward) = k_forward_col, k_forward_colj_sets, ... (k_forward, k_adjoint, k_apply)
+#if QD_COL_HJ
+#define QD_COL_HJ_TAG _colj
+#else
+#define QD_COL_HJ_TAG _col
 #endif
-// With QD_COL_SENS 1 (set by qd_col_sens.hip / qd_colj_sens.hip, objects of their own): the sensitivity form of the ADJOINT sweep,
-// k_adjoint_col_sens / k_adjoint_colj_sens (model-constant sensitivities, qd_optim_evalGradF_model with option sens_lean).  dM/d theta of a
-// detuning, a self-Kerr or a cross-Kerr coefficient is diagonal and time-independent, so d objective / d theta is a weighted sum over the
-// elements of W[e] = sum over the sub-steps of kbar_e.x z_e.y - kbar_e.y z_e.x, with the integer weights of qd_sens.h.  A thread keeps
-// W of its EPT elements in fp64 registers across the time loop - two fma per element and sub-step where kbar and z are at hand, nothing
-// per constant - and weights, reduces and stores the sens_count(Q) sums once per task, to the task's own row of SweepArgs::S.tred
-// [nslice][nb][sens_count(Q)] (no atomics: the host adds the rows in a fixed order).  Only the adjoint kernel of the diagonal-split
-// stationary instantiations is built; the forward sweep of the call is the plain k_forward_col / k_forward_colj.  Without the flag this
-// file preprocesses to the text it had before the form existed.
-#ifndef QD_COL_SENS
-#define QD_COL_SENS 0
+#if QD_COL_FORM == QD_FORM_PLAIN
+#define QD_COL_FORM_TAG
+#elif QD_COL_FORM == QD_FORM_SETS
+#define QD_COL_FORM_TAG _sets
+#elif QD_COL_FORM == QD_FORM_VARS
+#define QD_COL_FORM_TAG _vars
+#elif QD_COL_FORM == QD_FORM_SENS
+#define QD_COL_FORM_TAG _sens
+#elif QD_COL_FORM == QD_FORM_PAIR
+#define QD_COL_FORM_TAG _pair
+#else
+#error "QD_COL_FORM: a value of qd::Form"
 #endif
-#if QD_COL_SENS && (QD_COL_SETS || QD_COL_VARS)
-#error "QD_COL_SENS: a single evaluation - not together with QD_COL_SETS or QD_COL_VARS"
-#endif
-// With QD_COL_PAIR 1 (set by qd_col_pair.hip, objects of their own): the pair form of the FORWARD sweep, k_forward_col_pair (forward sweeps
-// on Hermitian pairs, option pair_hermitian).  The Lindblad operator is complex-linear on vec(rho) and maps Hermitian to Hermitian, and
-// so is every step of the stationary solve: state ic of the launch is X = rho_a + i rho_b of two Hermitian initial conditions, and the
-// kernel propagates it like any other state.  The form differs from the plain one in the per-time-step penalty block alone, which sums
-// the two members apart - their diagonals are the real and the imaginary part of X's - and in the two results it writes per state,
-// pen_out[2 ic] and pen_out[2 ic + 1].  Only the forward kernel of the stationary instantiations without coupling is built.  Without
-// the flag this file preprocesses to the text it had before the form existed.
-#ifndef QD_COL_PAIR
-#define QD_COL_PAIR 0
-#endif
-#if QD_COL_PAIR && (QD_COL_SETS || QD_COL_VARS || QD_COL_SENS || QD_COL_HJ)
-#error "QD_COL_PAIR: a single evaluation of a system without coupling - not together with another form"
-#endif
-#if QD_COL_SETS || QD_COL_VARS
+#define QD_COL_CAT_(a, b, c) a##b##c
+#define QD_COL_CAT(a, b, c) QD_COL_CAT_(a, b, c)
+#define QD_COLK(base) QD_COL_CAT(base, QD_COL_HJ_TAG, QD_COL_FORM_TAG)
+// (col_per_set below, for the preprocessor: the table addresses are macros)
+#define QD_COL_PER_SET (QD_COL_FORM == QD_FORM_SETS || QD_COL_FORM == QD_FORM_VARS)
+#if QD_COL_PER_SET
 #define QD_COL_CTL(A, ic) (A.ctl + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * A.ctl_set)
 #define QD_COL_GAUGE_TAB(A, ic) (gauge_tab(A) + (size_t)((unsigned)(ic) / (unsigned)A.nb_set) * gauge_set(A))
 #else
@@ -77,6 +87,19 @@
 #endif
 
 namespace qd {
+
+// What the unit's form is, stated once: every test below names one of these (or, in device code, one form)
+constexpr Form col_form = (Form)QD_COL_FORM;
+constexpr bool col_coupled = QD_COL_HJ != 0;
+constexpr bool col_per_set = QD_COL_PER_SET;                                    // reads the control and phasor tables of the task's set
+constexpr bool col_per_variant = col_form == Form::Vars;                        // ... and the model constants of its variant
+constexpr bool col_has_forward = col_form != Form::Sens;                        // the forward kernel is built
+constexpr bool col_has_adjoint = col_form != Form::Pair;                        // the adjoint kernel is built
+constexpr bool col_has_krylov = col_form == Form::Plain;                        // the Krylov instantiation (KRY = true)
+// the plain-Neumann instantiations (SPLIT = false); every unit has the diagonal-split ones
+constexpr bool col_has_plain_neumann = !col_coupled && (col_form == Form::Plain || col_form == Form::Sets || col_form == Form::Pair);
+constexpr bool col_has_apply = col_form == Form::Plain;                         // the operator application
+static_assert(!(col_coupled && col_form == Form::Pair), "no pair form of the coupled kernels: a unit that is not built");
 
 constexpr unsigned COLB = 1024;  // bytes per padded column: 64 rows x 16 B
 // Krylov solver of these kernels (ColTeam::kry_*): restart length.  Basis V[0 .. MR], preconditioned basis Z[0 .. MR - 1], the parked
@@ -113,7 +136,7 @@ enum : int { KET_NONE = 0, KET_BOTTOM = 1, KET_INTERIOR = 2, KET_TOP = 3 };
 #define QD_COL_GAUGE_SCOL 1
 #endif
 
-// The model constants ColLean::init derives a kernel's values from, read from the kernel argument (every form but QD_COL_VARS)
+// The model constants ColLean::init derives a kernel's values from, read from the kernel argument (every form but Vars)
 struct ColSysConsts {
   const DevSys& S;
   __device__ __forceinline__ double detune(int k) const { return S.detune[k]; }
@@ -565,7 +588,7 @@ struct ColTeam {
     __syncthreads();  // zero fill complete
   }
 
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   // The task about to run belongs to variant ic / nb_set: where that is not the variant of the workgroup's previous task (*cur; -1 before
   // the first), everything init derived from the model constants is derived again from the variant's block (ColLean::init<.., false>).
   // Workgroup-uniform; the barriers fence the column table, which every wave reads.  palpha = 0: the next set_alpha forms
@@ -1416,7 +1439,7 @@ __device__ __forceinline__ int slice_start(const SweepArgs& A, int sl) {
   return (int)((long long)A.ntime * sl / A.nslice) * A.nstages;
 }
 
-// Pair form (QD_COL_PAIR): where the owner of a diagonal element keeps member b's penalty sum - one double per thread behind the column
+// Pair form: where the owner of a diagonal element keeps member b's penalty sum - one double per thread behind the column
 // table, the 8 x blockDim.x bytes col_launch adds to the launch.  A second accumulator in registers would live across the pass loop,
 // which has none to spare.
 template <class TM>
@@ -1430,7 +1453,7 @@ __device__ __forceinline__ double* col_pair_word(unsigned char* smem, int N) {
 template <int Q, int EPT, bool SPLIT, bool USLOT = false, bool SKIP = false, bool KRY = false>
 __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const SweepArgs A) {
   static_assert(!KRY || (SPLIT && !SKIP), "the Krylov solver runs on the diagonal-split form");
-  constexpr bool HJ = QD_COL_HJ;
+  constexpr bool HJ = col_coupled;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // (ket classes: where the waves share the level of oscillator 0 - stationary diagonal-split solver, no coupling)
   typedef ColTeam<Q, EPT, SPLIT, USLOT, SKIP, HJ, SPLIT && USLOT && !KRY && !HJ> TM;
@@ -1439,7 +1462,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   tm.init(S, smem);
   if constexpr (KRY) tm.init_kry(A);
   __shared__ unsigned task_slot, carry_slot;
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   int curvar = -1;  // variant of the workgroup's previous task (ColTeam::enter_variant)
 #endif
   const int dim = S.dim, ntask = A.nb * A.nslice;
@@ -1448,7 +1471,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   const bool leak = pen_on && A.leak_on && tm.st.row_is_guard(S);
   for (int task = A.sched ? sched_next(A.sched, &task_slot) : (int)blockIdx.x; task < ntask; task = A.sched ? sched_next(A.sched, &task_slot) : ntask) {
   const int ic = task % A.nb, sl = task / A.nb;
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   tm.enter_variant(A, ic, &curvar);
 #endif
   const int s_lo = slice_start(A, sl), s_hi = slice_start(A, sl + 1);
@@ -1464,9 +1487,9 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   double pen_local = 0.0, pen_uniform [[maybe_unused]] = 0.0;  // (no uniform part in the pair form)
   // (pair form: pen_local sums member a; member b's sum is the thread's word of LDS, touched by the owner of a diagonal element once
   //  per full time step and addressed where it is used - nothing of it lives across the pass loop)
-  constexpr bool paired = QD_COL_PAIR != 0;
+  constexpr bool paired = col_form == Form::Pair;
   if constexpr (paired) col_pair_word<TM>(smem, S.N)[threadIdx.x] = 0.0;
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   // A time-sliced sweep of this form carries every thread's penalty sum from slice to slice (qd_col_vars.h: one block of
   // COL_VARS_PEN_STRIDE doubles per state, the uniform part in its last word) and reduces it once, behind the last slice: the additions
   // of a thread are those of the unsliced sweep in the same order, so a sliced call returns the bits of an unsliced one - penalties
@@ -1629,7 +1652,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
   }
   store_state(A.xT + (size_t)ic * 2 * dim, x, false);
   if (A.traj && sl == A.nslice - 1) store_state(A.traj + ((size_t)A.nsub * A.nb + ic) * 2 * dim, x, false);
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   if (A.sched && sl < A.nslice - 1) {  // not the last slice: the thread's sum travels on
     double* pcarry = col_vars_pen_carry(A) + (size_t)ic * COL_VARS_PEN_STRIDE;
     pcarry[threadIdx.x] = pen_local;
@@ -1647,7 +1670,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
 #else
   double v[1] = {pen_local};
   tm.template sum<1>(v);
-#if QD_COL_PAIR
+#if QD_COL_FORM == QD_FORM_PAIR
   // the members' sums apart (an odd batch has no second member in its last pair: A.paired = the number of members)
   double vb[1] = {col_pair_word<TM>(smem, S.N)[threadIdx.x]};
   tm.template sum<1>(vb);
@@ -1675,7 +1698,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_forward)(const
 template <int Q, int EPT, bool SPLIT, bool USLOT = false, bool SKIP = false, bool KRY = false>
 __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const SweepArgs A) {
   static_assert(!KRY || (SPLIT && !SKIP), "the Krylov solver runs on the diagonal-split form");
-  constexpr bool HJ = QD_COL_HJ;
+  constexpr bool HJ = col_coupled;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef ColTeam<Q, EPT, SPLIT, USLOT, SKIP, HJ> TM;
   const DevSys& S = A.S;
@@ -1683,7 +1706,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
   tm.init(S, smem);
   if constexpr (KRY) tm.init_kry(A);
   __shared__ unsigned task_slot, carry_slot;
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   int curvar = -1;  // variant of the workgroup's previous task (ColTeam::enter_variant)
 #endif
   const int dim = S.dim, ntask = A.nb * A.nslice;
@@ -1693,7 +1716,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
   for (int task = A.sched ? sched_next(A.sched, &task_slot) : (int)blockIdx.x; task < ntask; task = A.sched ? sched_next(A.sched, &task_slot) : ntask) {
   // backwards in time: task slice sl covers the time slice nslice - 1 - sl
   const int ic = task % A.nb, sl = task / A.nb;
-#if QD_COL_VARS
+#if QD_COL_FORM == QD_FORM_VARS
   tm.enter_variant(A, ic, &curvar);
 #endif
   const int s_lo = slice_start(A, A.nslice - 1 - sl), s_hi = slice_start(A, A.nslice - sl);
@@ -1706,7 +1729,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
     for (int j = 0; j < EPT; j++) xb[j] = tm.st.ok(j) ? make_double2(xbT[tm.st.elem(j)], xbT[dim + tm.st.elem(j)]) : make_double2(0.0, 0.0);
   }
   const double jbar_pen = A.jbar[ic * 3 + 0];
-#if QD_COL_SENS
+#if QD_COL_FORM == QD_FORM_SENS
   // W of the thread's elements over the sub-steps of this task (the sensitivity form, see the top of the file)
   double wacc[EPT];
 #pragma unroll
@@ -1795,7 +1818,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
         }
       }
       tm.publish(z);
-#if QD_COL_SENS
+#if QD_COL_FORM == QD_FORM_SENS
       // kbar^T (dM/d theta) z of the diagonal model operators, before the weights: kbar (h-scaled) and z are in ONE frame here, the lab
       // frame - the adjoint solve knows no other, and the forward sweep stores the stage as the lab-frame by-product z = U^dag z~ U
       // whatever frame it solves in (ColTeam::stage, A.ztraj) - as the ladder contraction below already relies on.  Padding elements
@@ -1838,7 +1861,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
         d0[dim + tm.st.elem(j)] = xb[j].y;
       }
   }
-#if QD_COL_SENS
+#if QD_COL_FORM == QD_FORM_SENS
   {  // once per task: the integer weights of the thread's elements from their level digits (qd_sens.h), the workgroup totals, the row
     constexpr int NS = sens_count(Q);
     double sacc[NS];
@@ -1862,7 +1885,7 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_adjoint)(const
 template <int Q, int EPT, bool SPLIT>
 __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_apply)(const DevSys S, const double* __restrict__ ctlrow, int transpose, const double* __restrict__ xin,
                                                               double* __restrict__ yout) {
-  constexpr bool HJ = QD_COL_HJ;
+  constexpr bool HJ = col_coupled;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef ColTeam<Q, EPT, SPLIT, false, false, HJ> TM;
   TM tm;
@@ -1888,15 +1911,14 @@ __global__ void __launch_bounds__(col_max_threads(EPT)) QD_COLK(k_apply)(const D
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side: the launchers, one text for both units - each instantiates them for its own kernels (QD_COLK) and coupling flag (QD_COL_HJ)
+// host side: the launchers, one text for every unit - each instantiates them for its own kernels (QD_COLK), form and coupling
 // ---------------------------------------------------------------------------------------------
-// the entry points for systems with dipole-dipole coupling (qd_colj.hip); launch_sweep_col / launch_apply_col forward to them where S.hasJ
-hipError_t launch_sweep_colj(const SweepArgs& a, bool adjoint, hipStream_t st);
+// the operator application for systems with dipole-dipole coupling (qd_colj.hip); launch_apply_col forwards to it where S.hasJ
 hipError_t launch_apply_colj(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
 
 #define QD_COL_STR_(x) #x
 #define QD_COL_STR(x) QD_COL_STR_(x)
-#define QD_COLK_NAME(base) QD_COL_STR(QD_COLK(base))  // "k_forward_col" / "k_forward_colj": the name note_kernel records
+#define QD_COLK_NAME(base) QD_COL_STR(QD_COLK(base))  // "k_forward_col" / "k_forward_colj_sets": the name note_kernel records
 
 // the columns of a wave share the level indices of every oscillator but the stride-1 one (ColLean's USLOT)
 template <int EPT>
@@ -1924,19 +1946,15 @@ static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
   typedef ColLean<Q, EPT> ST;
   const int threads = 64 * (ST::ncols(a.S.N) / EPT);
   // (pair form: member b's penalty word per thread, col_pair_word; pairs are an error in every other form, and the other way round)
-  if ((a.paired != 0) != (QD_COL_PAIR != 0)) return hipErrorInvalidValue;
-  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0) + (QD_COL_PAIR ? sizeof(double) * (size_t)threads : 0);
-#if QD_COL_PAIR
-  // (the pair form has no adjoint kernel: an error, and nothing instantiated)
-  if (adjoint) return hipErrorInvalidValue;
-  auto kf = QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
-#elif QD_COL_SENS
-  // (the sensitivity form has no forward kernel - the forward sweep of its call is the plain one: an error, and nothing instantiated)
-  if (!adjoint) return hipErrorInvalidValue;
-  auto kf = QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
-#else
-  auto kf = adjoint ? QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY> : QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
-#endif
+  if ((a.paired != 0) != (col_form == Form::Pair)) return hipErrorInvalidValue;
+  const size_t lds = ST::lds_bytes(a.S.N) + (KRY ? ColTeam<Q, EPT, true>::kry_lds_extra(a.S.N) : 0) + (col_form == Form::Pair ? sizeof(double) * (size_t)threads : 0);
+  // (a direction the form has no kernel for - the pair form's adjoint, the sensitivity form's forward sweep, which is the plain one's:
+  //  an error, and nothing instantiated)
+  if (adjoint ? !col_has_adjoint : !col_has_forward) return hipErrorInvalidValue;
+  void (*kf)(const SweepArgs);
+  if constexpr (!col_has_adjoint) kf = QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
+  else if constexpr (!col_has_forward) kf = QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
+  else kf = adjoint ? QD_COLK(k_adjoint)<Q, EPT, SPLIT, USLOT, SKIP, KRY> : QD_COLK(k_forward)<Q, EPT, SPLIT, USLOT, SKIP, KRY>;
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
   note_kernel(adjoint ? 1 : 0, adjoint ? QD_COLK_NAME(k_adjoint) : QD_COLK_NAME(k_forward), Q, EPT, SPLIT, USLOT, SKIP, KRY);
@@ -1944,12 +1962,35 @@ static hipError_t col_launch(const SweepArgs& a, bool adjoint, hipStream_t st) {
   return hipGetLastError();
 }
 
-// The instantiation a sweep runs, from the run-time facts - the same for both directions.  Built: the Krylov solver (SweepArgs::use_gmres)
-// in the diagonal-split form that tests every pass; the stationary iteration in the plain and the diagonal-split form (neumann_split), each
-// with and without SKIP; every one of them in both USLOT forms.  With coupling (QD_COL_HJ) the diagonal-split forms without SKIP only: a
-// coupled sweep that asks for the plain Neumann iteration is never planned (qd_handle::col_sweep) and is an invalid value here.
+// What the unit's form asks of a sweep's arguments; a request the unit cannot serve is an error, never another kernel.
+//   every unit   its own coupling, and a solver it has an instantiation of
+//   Sets, Vars   a.nb states = a.nb / a.nb_set sets (Vars: a set is a variant), each reading its own control table
+//   Vars         the constants table, never a dense handle; a time-sliced forward sweep needs the carry buffer of the penalty sums
+//   Sens         the adjoint sweep of a single evaluation on the diagonal-split stationary iteration, with the stored stages and the buffer
+//                of the sums
+//   Pair         the forward sweep of a single evaluation on the stationary solvers, on a.nb = ceil(a.paired / 2) pairs, nothing stored,
+//                no in-loop penalty that reads off-diagonal elements
+static bool col_form_args_ok(const SweepArgs& a, bool adjoint) {
+  if ((a.S.hasJ != 0) != col_coupled || (a.use_gmres && !col_has_krylov)) return false;
+  if (col_per_set && !(a.nb_set >= 1 && a.nb % a.nb_set == 0)) return false;
+  if (col_per_variant && !(col_vars_tab(a) && !a.S.dense && (adjoint || !a.sched || col_vars_pen_carry(a)))) return false;
+  if (col_form == Form::Sens) return adjoint && a.neumann_split && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && a.S.tred && a.ztraj;
+  if (col_form == Form::Pair)
+    return !adjoint && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && a.paired >= 2 && a.nb == (a.paired + 1) / 2 && !a.traj && !a.ztraj &&
+           (!(a.gamma_penalty > 1e-13 && a.penalty_param > 1e-13) || (a.wjw && a.tg.objective_type == QD_OBJ_JMEASURE));
+  return true;
+}
+
+// The instantiation a sweep runs, from the run-time facts - the same for both directions and every form.  Built (the properties at the top
+// of this file say for which unit): the Krylov solver (SweepArgs::use_gmres) in the diagonal-split form that tests every pass; the
+// stationary iteration in the plain and the diagonal-split form (neumann_split), each with and without SKIP; every one of them in both
+// USLOT forms.  With coupling the diagonal-split forms without SKIP only: a coupled sweep that asks for the plain Neumann iteration is
+// never planned (qd_handle::col_sweep).  A Vars plan on the plain-Neumann or Krylov solver goes variant by variant (qd_optim.cpp), such a
+// Sens plan takes the general family (qd_optim_evalGradF_model).  What is not built is an invalid value here, and nothing of it is
+// instantiated.  (The order of the go() lines is the order in which the unit names its kernels: see go_sweep of qd_q32.hip.)
 template <int Q, int EPT>
 static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
+  if (!col_form_args_ok(a, adjoint)) return hipErrorInvalidValue;
   const bool uslot = col_uslot<EPT>(a.S);
   auto go = [&](auto split, auto skip, auto kry) {
     constexpr bool SPLIT = decltype(split)::value, SKIP = decltype(skip)::value, KRY = decltype(kry)::value;
@@ -1957,44 +1998,31 @@ static hipError_t col_sweep(const SweepArgs& a, bool adjoint, hipStream_t st) {
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-#if QD_COL_VARS || QD_COL_SENS
-  // the third form is built for the diagonal-split stationary iteration only (a plain-Neumann or Krylov plan goes variant by variant,
-  // qd_optim.cpp), and so is the sensitivity form (such a plan takes the general family, qd_optim_evalGradF_model): anything else is an
-  // error, and nothing of it is instantiated
-  if (a.use_gmres || !a.neumann_split) return hipErrorInvalidValue;
-  if constexpr (QD_COL_HJ) {
-    return go(yes, no, no);
-  } else {
-    const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;  // (the rule of the other forms)
-    return skip ? go(yes, yes, no) : go(yes, no, no);
+  if (a.use_gmres) {
+    if constexpr (col_has_krylov) return go(yes, no, yes);
+    else return hipErrorInvalidValue;
   }
-#else
-  if constexpr (QD_COL_SETS || QD_COL_PAIR) {  // (no SETS or pair form of the Krylov kernels: an error, and nothing instantiated)
-    if (a.use_gmres) return hipErrorInvalidValue;
-  } else {
-    if (a.use_gmres) return go(yes, no, yes);
+  // (SKIP: stopping tests skipped, see ColTeam::stage)
+  // (implicit midpoint only: the predictor compares the pass count of a sub-step with its predecessor's, and the sub-steps of a composite
+  //  step differ in size - IMR4 / IMR8 test every pass; nothing of this lives in the kernels)
+  const bool skip = !col_coupled && a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;
+  if (a.neumann_split) {
+    if constexpr (col_coupled) return go(yes, no, no);
+    else return skip ? go(yes, yes, no) : go(yes, no, no);
   }
-  if constexpr (QD_COL_HJ) {
-    return a.neumann_split ? go(yes, no, no) : hipErrorInvalidValue;
-  } else {
-    // (SKIP: stopping tests skipped, see ColTeam::stage)
-    // (implicit midpoint only: the predictor compares the pass count of a sub-step with its predecessor's, and the sub-steps of a composite
-    //  step differ in size - IMR4 / IMR8 test every pass; nothing of this lives in the kernels)
-    const bool skip = a.rel2 < 1e-30f && !a.col_noskip && a.nstages == 1;
-    if (a.neumann_split) return skip ? go(yes, yes, no) : go(yes, no, no);
-    return skip ? go(no, yes, no) : go(no, no, no);
-  }
-#endif
+  if constexpr (col_has_plain_neumann) return skip ? go(no, yes, no) : go(no, no, no);
+  else return hipErrorInvalidValue;
 }
 
 // One operator application.  SPLIT selects the kernel family that re-derives the diagonal from its compact form (uncoupled: the option
 // neumann_split = 1, test coverage); the coupled kernels are built in that form only and their entry point passes split = true.
 template <int Q, int EPT>
 static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const double* x, double* y, int nb, bool split, hipStream_t st) {
+  static_assert(col_has_apply && Q > 0, "the operator application belongs to the plain units");
   typedef ColLean<Q, EPT> ST;
   const size_t lds = ST::lds_bytes(S.N);
   auto kf = QD_COLK(k_apply)<Q, EPT, true>;
-  if constexpr (!QD_COL_HJ)
+  if constexpr (!col_coupled)
     if (!split) kf = QD_COLK(k_apply)<Q, EPT, false>;
   hipError_t e = set_lds(kf, lds);
   if (e != hipSuccess) return e;
@@ -2014,50 +2042,16 @@ static hipError_t col_apply(const DevSys& S, const double* ctlrow, int tr, const
     return hipErrorInvalidValue;                                                       \
   } while (0)
 
-#if QD_COL_SENS
-// The units of the sensitivity form: the adjoint sweep of a single evaluation on the diagonal-split stationary iteration, with the stored
-// stages and the buffer of the sums.  Anything else - a forward sweep included - is an error, never another kernel.
-static bool col_sens_args_ok(const SweepArgs& a, bool adjoint) {
-  return adjoint && !a.use_gmres && a.neumann_split && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && a.S.tred && a.ztraj;
-}
-#endif
-#if QD_COL_PAIR
-// The units of the pair form: the forward sweep of a single evaluation on the stationary solvers, on a.nb = ceil(a.paired / 2) pairs.
-// Anything else is an error, never another kernel.
-static bool col_pair_args_ok(const SweepArgs& a, bool adjoint) {
-  return !adjoint && !a.use_gmres && a.nb_set == 0 && !a.stepper_ee && !a.S.dense && !a.S.hasJ && a.paired >= 2 && a.nb == (a.paired + 1) / 2 &&
-         !a.traj && !a.ztraj && (!(a.gamma_penalty > 1e-13 && a.penalty_param > 1e-13) || (a.wjw && a.tg.objective_type == QD_OBJ_JMEASURE));
-}
-#endif
-#if QD_COL_SETS || QD_COL_VARS || QD_COL_SENS || QD_COL_PAIR
-#if !QD_COL_SENS && !QD_COL_PAIR
-// The SETS units (and the units of the third form, QD_COL_VARS: a set is a variant): a.nb states = a.nb / a.nb_set sets, each reading its
-// own control table.  A request they cannot serve - the Krylov solver, states that do not divide into sets - is an error, never another
-// kernel.
-static bool col_sets_args_ok(const SweepArgs& a) { return !a.use_gmres && a.nb_set >= 1 && a.nb % a.nb_set == 0; }
-#endif
-#if QD_COL_VARS
-// ... of the third form besides: the constants table, never a dense handle; a time-sliced forward sweep needs the carry buffer of the
-// penalty sums
-static bool col_vars_args_ok(const SweepArgs& a, bool adjoint) {
-  return col_sets_args_ok(a) && col_vars_tab(a) && !a.S.dense && (adjoint || !a.sched || col_vars_pen_carry(a));
-}
-#endif
-// One object per <Q, EPT> (QD_COL_SETS_Q, QD_COL_SETS_EPT on the command line: they compile side by side) holds that case's col_sweep and
-// with it its kernels; the object built without the two holds the unit's entry point, which reaches them through QD_COL_DISPATCH.
-template <int Q, int EPT>
-hipError_t QD_COLK(sweep_part)(const SweepArgs& a, bool adjoint, hipStream_t st);
-#ifdef QD_COL_SETS_Q
-template <>
-hipError_t QD_COLK(sweep_part)<QD_COL_SETS_Q, QD_COL_SETS_EPT>(const SweepArgs& a, bool adjoint, hipStream_t st) {
-  return col_sweep<QD_COL_SETS_Q, QD_COL_SETS_EPT>(a, adjoint, st);
-}
-#else
-template <> hipError_t QD_COLK(sweep_part)<2, 5>(const SweepArgs& a, bool adjoint, hipStream_t st);
-template <> hipError_t QD_COLK(sweep_part)<2, 8>(const SweepArgs& a, bool adjoint, hipStream_t st);
-template <> hipError_t QD_COLK(sweep_part)<3, 5>(const SweepArgs& a, bool adjoint, hipStream_t st);
-template <> hipError_t QD_COLK(sweep_part)<3, 8>(const SweepArgs& a, bool adjoint, hipStream_t st);
-#endif
-#endif
+// One object holds col_sweep<Q, EPT> of its unit and with it that case's kernels; the family's entry point (qd_col.hip) reaches it by the
+// unit's tag and <Q, EPT> through QD_COL_DISPATCH.  The plain units define all four parts, an object of qd_col_form.hip its one.
+template <Form F, bool HJ>
+struct ColUnit {};
+template <int Q, int EPT, Form F, bool HJ>
+hipError_t col_sweep_part(ColUnit<F, HJ>, const SweepArgs& a, bool adjoint, hipStream_t st);
+#define QD_COL_PART(Q, EPT)                                                                                                \
+  template <>                                                                                                              \
+  hipError_t col_sweep_part<Q, EPT>(ColUnit<col_form, col_coupled>, const SweepArgs& a, bool adjoint, hipStream_t st) { \
+    return col_sweep<Q, EPT>(a, adjoint, st);                                                                              \
+  }
 
 }  // namespace qd

@@ -18,15 +18,13 @@
 //     columns I' -+ post[k] +- post[l] through two more scalar offsets, weights that carry J_kl, and cos / sin(eta_kl t) from the control
 //     table row.  No diagonal entry: the diagonal-split solver's D, P and the column table are those of the uncoupled system.
 //
-// The device code (ColLean, ColTeam, the three kernels) and the launchers (col_launch, col_sweep, col_apply) are qd_col.h, shared with
-// qd_colj.hip; this unit instantiates them for systems without coupling, k_*_col, and holds the rest of the host side: availability,
-// slicing, the entry points.
+// The device code (ColLean, ColTeam, the three kernels) and the launchers (col_launch, col_sweep, col_apply) are qd_col.h, shared by
+// every unit of the family (the list: the top of qd_col.h).  This unit is the plain one for systems without coupling, k_*_col - qd_col.h
+// with its defaults -, and holds the rest of the host side: availability, slicing, the family's entry points.
 //
 // Reference semantics (paths relative to the reference repository): stencil include/mastereq.hpp:316-912 as instantiated by
 // src/mastereq.cpp:1464-1709 (two oscillators) / :1713-2018 (three); IMR forward / adjoint src/timestepper.cpp:584-694,
 // Neumann :697-727, time loops :96-253, penalties :256-339, gradient coefficients include/mastereq.hpp:553-604.
-#define QD_COLK(base) base##_col
-#define QD_COL_HJ false
 #include "qd_col.h"
 
 namespace qd {
@@ -70,9 +68,27 @@ bool collean_available(const DevSys& S, const TuneOpts& o) {
   return !qubit && S.post[S.Q - 1] == 1;
 }
 
-hipError_t launch_sweep_col(const SweepArgs& a, bool adjoint, hipStream_t st) {
-  if (a.S.hasJ) return launch_sweep_colj(a, adjoint, st);
-  QD_COL_DISPATCH(a.S, col_sweep, a, adjoint, st);
+QD_COL_PART(2, 5)
+QD_COL_PART(2, 8)
+QD_COL_PART(3, 5)
+QD_COL_PART(3, 8)
+
+// The family's sweep entry point: the part of the unit (form, a.S.hasJ) for the system's <Q, EPT>.  The parts of the other units are
+// objects of their own (qd_colj.hip, qd_col_form.hip); a unit that is not built - the pair form with coupling - is an error.
+template <Form F, bool HJ>
+static hipError_t col_unit(const SweepArgs& a, bool adjoint, hipStream_t st) {
+  QD_COL_DISPATCH(a.S, col_sweep_part, ColUnit<F, HJ>{}, a, adjoint, st);
+}
+hipError_t launch_sweep_col(Form form, const SweepArgs& a, bool adjoint, hipStream_t st) {
+  const bool hj = a.S.hasJ != 0;
+  switch (form) {
+    case Form::Plain: return hj ? col_unit<Form::Plain, true>(a, adjoint, st) : col_unit<Form::Plain, false>(a, adjoint, st);
+    case Form::Sets: return hj ? col_unit<Form::Sets, true>(a, adjoint, st) : col_unit<Form::Sets, false>(a, adjoint, st);
+    case Form::Vars: return hj ? col_unit<Form::Vars, true>(a, adjoint, st) : col_unit<Form::Vars, false>(a, adjoint, st);
+    case Form::Sens: return hj ? col_unit<Form::Sens, true>(a, adjoint, st) : col_unit<Form::Sens, false>(a, adjoint, st);
+    case Form::Pair: return hj ? hipErrorInvalidValue : col_unit<Form::Pair, false>(a, adjoint, st);
+  }
+  return hipErrorInvalidValue;
 }
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st) {
   if (S.hasJ) return launch_apply_colj(S, ctlrow, transpose, x, y, nb, st);

@@ -1,4 +1,4 @@
-// qd_col_vars.h - constants table of a model-parameter ensemble on the lean column kernels (qd_col.h under QD_COL_VARS: k_*_col_vars /
+// qd_col_vars.h - constants table of a model-parameter ensemble on the lean column kernels (qd_col.h, Form::Vars: k_*_col_vars /
 // k_*_colj_vars; qd_optim_evalF_ensemble_model / qd_optim_evalGradF_ensemble_model).
 //
 // One control vector is evaluated on nvar variants of the standard Hamiltonian model that differ in transition frequencies, self-Kerr

@@ -1244,17 +1244,10 @@ int qd_handle::arm_slices(qd::SweepArgs& a, int nb, int which) {
 // The sweep kernel of a plan, forward or adjoint, by (family, form): each lean family picks its instantiation once for both directions.
 // A form a family has no kernels for is an error, never another kernel.
 static hipError_t launch_sweep(const SweepArgs& a, const SweepPlan& plan, bool adjoint, const TuneOpts& opts, hipStream_t st) {
-  typedef hipError_t (*slot_fn)(const SweepArgs&, bool, const TuneOpts&, hipStream_t);
-  typedef hipError_t (*col_fn)(const SweepArgs&, bool, hipStream_t);
-  // index Form: Plain, Sets, Vars, Sens, Pair
-  static const slot_fn f32[5] = {launch_sweep_f32, launch_sweep_f32_sets, launch_sweep_f32_vars, nullptr, nullptr};
-  static const slot_fn slot[5] = {launch_sweep_lean64, launch_sweep_lean64_sets, launch_sweep_lean64_vars, launch_sweep_lean64_sens, nullptr};
-  static const col_fn col[5] = {launch_sweep_col, launch_sweep_col_sets, launch_sweep_col_vars, launch_sweep_col_sens, launch_sweep_col_pair};
-  const int f = (int)plan.form;
   switch (plan.family) {
-    case Family::F32: return f32[f] ? f32[f](a, adjoint, opts, st) : hipErrorInvalidValue;
-    case Family::Slot: return slot[f] ? slot[f](a, adjoint, opts, st) : hipErrorInvalidValue;
-    case Family::Col: return col[f] ? col[f](a, adjoint, st) : hipErrorInvalidValue;
+    case Family::F32: return launch_sweep_f32(plan.form, a, adjoint, opts, st);
+    case Family::Slot: return launch_sweep_lean64(plan.form, a, adjoint, opts, st);
+    case Family::Col: return launch_sweep_col(plan.form, a, adjoint, st);
     default: return launch_general(plan.form, adjoint, a, plan.cfg, st);  // General and Global: the variant says which
   }
 }

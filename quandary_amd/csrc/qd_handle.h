@@ -91,15 +91,7 @@ struct HBuf {
 // Col: lean column kernels (qd_col.hip); Global: vectors in global memory, teams of workgroups (qd_big.h, variant 16).
 enum class Family { General = 0, F32 = 1, Slot = 2, Col = 3, Global = 4 };
 
-// Form of the sweep kernels, the second axis of the same decision (every family has the plain form, a missing one is an error):
-// Plain: one control vector, one set of model constants; Sets: one control table per parameter set (qd_handle::sets without a constants
-// table); Vars: one block of model constants per ensemble variant and one control table (sets with qd_handle::vars_tab); Sens: the adjoint
-// sweep of a single evaluation that also sums the model-constant sensitivities (qd_handle::sens); Pair: the forward sweep of a single
-// evaluation on Hermitian pairs (qd_handle::pair_gate turns a plain plan into it; the lean column family alone has the kernels).
-enum class Form : int { Plain = 0, Sets = 1, Vars = 2, Sens = 3, Pair = 4 };
-// the pair form of the lean column forward sweep (qd_col_pair.hip: k_forward_col_pair): a.paired members as a.nb = ceil(a.paired / 2)
-// states; an adjoint sweep, a Krylov request, a coupled system or an in-loop penalty that reads off-diagonal elements is an error
-hipError_t launch_sweep_col_pair(const SweepArgs& a, bool adjoint, hipStream_t st);
+// (Form, the second axis of the same decision: qd_internal.h, shared with the kernel units.)
 
 // Gershgorin bounds of a row of M for the current parameters (qd_handle::row_bounds) and the largest alpha = |h| / 2 of the step
 // schedule: what every solver gate looks at, computed once per plan

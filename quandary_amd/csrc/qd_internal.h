@@ -101,7 +101,7 @@ struct SweepArgs {
   // (timestepper.cpp:262-270, :304-315); tabulated once per handle so that the sweep kernels of qd_col.hip need no exp() per step
   const double* wjw;
   int use_gmres;  // 0: Neumann; 1: in-kernel GMRES, Krylov basis in LDS (one element per thread, small dim); 2: basis in global memory (kry)
-  // Hermitian pairs (pair form of the lean column forward sweep, qd_col_pair.hip; qd_handle::pair_gate): 0, or the number nl of Hermitian
+  // Hermitian pairs (pair form of the lean column forward sweep, Form::Pair of qd_col.h; qd_handle::pair_gate): 0, or the number nl of Hermitian
   // initial conditions whose pairs X_p = rho_2p + i rho_2p+1 are the nb = ceil(nl / 2) states of the launch - the penalty block of that
   // form sums the members of a pair apart, pen_out[2 ic] and pen_out[2 ic + 1].  (In what was padding behind use_gmres: size and
   // offsets of the struct stay.)
@@ -240,7 +240,34 @@ hipError_t launch_controls2(const DevCtlDesc& d, const double* params, const dou
                             unsigned long long* zero_me, hipStream_t st);
 hipError_t launch_apply(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb,
                         const LaunchCfg& cfg, hipStream_t st);
-// The sweep kernels of the general family (qd_inst.hip) in the form the plan names (Form, qd_handle.h), forward or adjoint; every form runs
+// Form of the sweep kernels, the second axis of a sweep's plan beside the kernel family (qd_handle.h: Family, SweepPlan).  Every family
+// has the plain form; a form a family has no kernels for is an error, never another kernel.  A family's sweep entry point takes the form
+// and runs the instantiation the plain form picks for the same arguments.
+//   Plain  one control vector, one set of model constants
+//   Sets   one control table per parameter set of a.nb_set states (qd_handle::sets without a constants table; parameter-set batch,
+//          qd_optim_evalGradF_batch).  Lean families: the stationary iterations only - a Krylov request is an error
+//   Vars   one block of model constants per ensemble variant of a.nb_set states and ONE control table (sets with qd_handle::vars_tab, the
+//          table of qd_col_vars.h in a.S.hcr; qd_optim_evalGradF_ensemble_model).  Lean slot families: the stationary iterations; lean
+//          column family: the diagonal-split stationary iteration - anything else, or a missing table, is an error
+//   Sens   the adjoint sweep of a single evaluation that also sums kbar^T (dM/d theta) z over all sub-steps for the detunings, self-Kerr
+//          and cross-Kerr coefficients (qd_handle::sens; qd_optim_evalGradF_model), one row of sens_columns(Q) sums per task into a.S.tred.
+//          No forward kernel - the forward sweep of the call is the plain one.  Lean slot family: fp64 only, [nb] rows, the stationary
+//          iterations; lean column family: [nslice][nb] rows, the diagonal-split stationary iteration.  A forward or Krylov request, a
+//          missing a.S.tred or a.ztraj is an error
+//   Pair   the forward sweep of a single evaluation on Hermitian pairs: a.paired members as a.nb = ceil(a.paired / 2) states
+//          (qd_handle::pair_gate turns a plain plan into it).  The lean column family alone, stationary iterations without coupling; an
+//          adjoint sweep, a Krylov request, a coupled system or an in-loop penalty that reads off-diagonal elements is an error
+enum class Form : int { Plain = 0, Sets = 1, Vars = 2, Sens = 3, Pair = 4 };
+// (the same numbers for the preprocessor: a unit compiled once per form gets its form on the command line, -DQD_COL_FORM= of qd_col.h)
+#define QD_FORM_PLAIN 0
+#define QD_FORM_SETS 1
+#define QD_FORM_VARS 2
+#define QD_FORM_SENS 3
+#define QD_FORM_PAIR 4
+static_assert((int)Form::Plain == QD_FORM_PLAIN && (int)Form::Sets == QD_FORM_SETS && (int)Form::Vars == QD_FORM_VARS &&
+              (int)Form::Sens == QD_FORM_SENS && (int)Form::Pair == QD_FORM_PAIR, "QD_FORM_* are the values of Form");
+
+// The sweep kernels of the general family (qd_inst.hip) in the form the plan names, forward or adjoint; every form runs
 // the template arguments the plain one picks for the same arguments:
 //   Plain  one control vector, one set of model constants - every variant, the global-memory kernels (variant 16) included
 //   Sets   one control table per set of a.nb_set states (-DQD_SETS=1): every LDS variant, of the standard Hamiltonian model and of the
@@ -251,7 +278,6 @@ hipError_t launch_apply(const DevSys& S, const double* ctlrow, int transpose, co
 //          and cross-Kerr coefficients, [nb][2 Q + npairs] into a.S.tred (-DQD_SENS=1: k_adjoint_sens, qd_sens.h): the LDS variants of
 //          the standard Hamiltonian model, implicit-midpoint family, no forward sweep
 // A form that is not built for the arguments is an error, never another kernel.
-enum class Form : int;
 hipError_t launch_general(Form form, bool adjoint, const SweepArgs& a, const LaunchCfg& cfg, hipStream_t st);
 inline int sens_columns(int Q) { return 2 * Q + Q * (Q - 1) / 2; }
 // control tables of nset parameter vectors in one launch: params [nset][ndesign] -> table [nset][nrows][cs], table2 [nset][nrows2][cs]
@@ -285,52 +311,25 @@ hipError_t launch_reduce_coeff_sets(const double* coeff, int nb, int ncol, doubl
 hipError_t launch_grad_sets(const DevCtlDesc& d, const double* params, const double* table, size_t table_set, int cs, int nsub, const double* coeffsum,
                             const double* etable, size_t etable_set, int nstep, double ebar, double* grad, int ndesign, int nset, hipStream_t st);
 // fp32-mixed sweeps of all-qubit Lindblad systems (qd_q32.hip); the trajectory is [nsub+1][nb][dim] float2
-// (one entry point per lean family for both sweeps, adjoint = 0 forward / 1 adjoint: the adjoint kernel reads the primal stages in the
-// element order the forward kernel of the SAME instantiation wrote, so the instantiation is chosen once, whatever the direction)
-hipError_t launch_sweep_f32(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+// (one entry point per lean family for both sweeps and every form, adjoint = 0 forward / 1 adjoint: the adjoint kernel reads the primal
+// stages in the element order the forward kernel of the SAME instantiation wrote, so the instantiation is chosen once, whatever the
+// direction and the form - Form above)
+hipError_t launch_sweep_f32(Form form, const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_f32(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, int nrep, int mfma,
                             hipStream_t st);
-// the same lean slot kernel instantiated in fp64: Neumann sweeps of the 2^5 Lindblad system (QD_PRECISION_F64)
+// the same lean slot kernel instantiated in fp64: Neumann sweeps of the 2^5 Lindblad system (QD_PRECISION_F64).  In the Sets and Vars forms
+// of both slot families the uncoupled 2^5 system picks one or two elements per thread from ALL states of the launch, a.nb = sets x states
+// per set (option lean64_sb pins it, as for the single sweep)
 bool lean64_available(const DevSys& S, const TuneOpts& o);
-hipError_t launch_sweep_lean64(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
-// the stationary-iteration sweeps of both lean slot families with one control table per set of a.nb_set states (qd_q32.hip compiled
-// with -DQD_SETS=1: k_forward_q32_sets / k_adjoint_q32_sets); a Krylov request is an error.  The uncoupled 2^5 system picks one or two
-// elements per thread from ALL states of the launch, a.nb = sets x states per set (option lean64_sb pins it, as for the single sweep)
-hipError_t launch_sweep_f32_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
-hipError_t launch_sweep_lean64_sets(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
-// ... with one block of model constants per set of a.nb_set states and ONE control table (qd_q32.hip compiled with -DQD_VARS=1:
-// k_forward_q32_vars / k_adjoint_q32_vars, the instantiations of the SETS launchers; the table of qd_col_vars.h in a.S.hcr): a Krylov
-// request or a missing table is an error.  Elements per thread of the uncoupled 2^5 system as in the SETS form, from a.nb = variants x states
-hipError_t launch_sweep_f32_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
-hipError_t launch_sweep_lean64_vars(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
-// the sensitivity form of the fp64 adjoint sweep (qd_q32.hip compiled with -DQD_SENS=1: k_adjoint_q32_sens, the instantiation
-// launch_sweep_lean64 picks for the same arguments): the stationary iterations only, and the adjoint direction only - a forward or
-// Krylov request, a missing a.S.tred or a.ztraj is an error.  Every state stores its sums of kbar^T (dM/d theta) z to its own row of
-// a.S.tred, [nb][sens_columns(Q)].
-hipError_t launch_sweep_lean64_sens(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
+hipError_t launch_sweep_lean64(Form form, const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st);
 hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, hipStream_t st);
-// lean column kernels (qd_col.hip): Lindblad Neumann sweeps of density matrices with 33..64 rows and runtime level counts
+// lean column kernels (qd_col.hip): Lindblad Neumann sweeps of density matrices with 33..64 rows and runtime level counts, with and
+// without dipole-dipole coupling (k_*_col* / k_*_colj*: the entry points look at S.hasJ)
 bool collean_available(const DevSys& S, const TuneOpts& o);
 int col_slices(int nb, int ntime, const TuneOpts& o);  // time slices of a lean column sweep (1 = none)
 size_t col_krylov_doubles(int nb, int nslice);  // size of SweepArgs::kry for the Krylov solver of the lean column kernels
-hipError_t launch_sweep_col(const SweepArgs& a, bool adjoint, hipStream_t st);
+hipError_t launch_sweep_col(Form form, const SweepArgs& a, bool adjoint, hipStream_t st);
 hipError_t launch_apply_col(const DevSys& S, const double* ctlrow, int transpose, const double* x, double* y, int nb, const TuneOpts& o, hipStream_t st);
-// their stationary-iteration sweeps with one control table per set of a.nb_set states (qd_col_sets.hip / qd_colj_sets.hip: k_*_col_sets,
-// k_*_colj_sets, the instantiation launch_sweep_col picks for the same arguments); a Krylov request is an error.  The first forwards to
-// the second where S.hasJ.
-hipError_t launch_sweep_col_sets(const SweepArgs& a, bool adjoint, hipStream_t st);
-hipError_t launch_sweep_colj_sets(const SweepArgs& a, bool adjoint, hipStream_t st);
-// ... with one block of model constants per set as well (qd_col_vars.hip / qd_colj_vars.hip: k_*_col_vars, k_*_colj_vars; the table of
-// qd_col_vars.h): the diagonal-split stationary instantiations only - a Krylov or plain-Neumann request is an error.  The first forwards
-// to the second where S.hasJ.
-hipError_t launch_sweep_col_vars(const SweepArgs& a, bool adjoint, hipStream_t st);
-hipError_t launch_sweep_colj_vars(const SweepArgs& a, bool adjoint, hipStream_t st);
-// the sensitivity form of their adjoint sweep (qd_col_sens.hip / qd_colj_sens.hip: k_adjoint_col_sens, k_adjoint_colj_sens, the
-// instantiation launch_sweep_col picks for the same arguments): the diagonal-split stationary instantiations only, and the adjoint
-// direction only - a forward, Krylov or plain-Neumann request is an error.  Every task (state, time slice) stores its sums of
-// kbar^T (dM/d theta) z to its own row of a.S.tred, [nslice][nb][sens_columns(Q)].  The first forwards to the second where S.hasJ.
-hipError_t launch_sweep_col_sens(const SweepArgs& a, bool adjoint, hipStream_t st);
-hipError_t launch_sweep_colj_sens(const SweepArgs& a, bool adjoint, hipStream_t st);
 LaunchCfg pick_config(const DevSys& S, int nb, const TuneOpts& o, bool want_gmres = false);
 size_t krylov_doubles(const DevSys& S, int nb);
 size_t big_work_doubles(const DevSys& S, int nb);

@@ -19,7 +19,6 @@
 #include "qd_device.h"
 #include "qd_big.h"
 #include "qd_gauge.h"
-#include "qd_handle.h"  // (Form: the index of the dispatch table below)
 
 namespace qd {
 
@@ -762,7 +761,7 @@ static bool form_args_ok(Form form, const SweepArgs& a, const LaunchCfg& cfg) {
     case Form::Sets: return sets_axis && (cfg.qubit == 2) == (a.S.dense != 0) && (!a.S.dense || (a.S.gtab && a.gtab_set));
     case Form::Vars: return sets_axis && model && a.S.hcr != nullptr;
     case Form::Sens: return model && a.nb_set == 0 && !a.stepper_ee && a.S.tred && a.ztraj;
-    case Form::Pair: return false;  // (the lean column family alone: qd_col_pair.hip)
+    case Form::Pair: return false;  // (the lean column family alone: qd_col.h)
   }
   return false;
 }

@@ -1409,7 +1409,7 @@ extern "C" int qd_optim_last_batch_sets(const qd_optim* o) { return o ? o->last_
 // (qd_sens.h); kbar is never stored, so the sums cannot be formed anywhere else.  The general family has that kernel for every system
 // (k_adjoint_sens): both sweeps are planned there, as options no_collean / no_lean64 would, and the handle is put back afterwards.
 // Under option sens_lean a call whose own plan is the diagonal-split stationary iteration of the lean column family stays on it: the
-// forward sweep as planned, the adjoint sweep on k_adjoint_col_sens / k_adjoint_colj_sens (qd_col.h under QD_COL_SENS), which keeps
+// forward sweep as planned, the adjoint sweep on k_adjoint_col_sens / k_adjoint_colj_sens (qd_col.h, Form::Sens), which keeps
 // w = kbar.x z.y - kbar.y z.x summed per element over the sub-steps and applies the integer weights once per task.  Under option
 // sens_slot a call whose own plan is an fp64 stationary iteration of the lean slot family (2^4 / 2^5 Lindblad, with or without Jkl) stays
 // there the same way: forward sweep k_forward_q32, adjoint sweep k_adjoint_q32_sens (qd_q32.hip under QD_SENS), one row of sums per state.
@@ -1462,7 +1462,7 @@ extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_obj
   // option sens_lean: both sweeps as the handle's own options plan them - where that is the lean column family and the adjoint plan has
   // a sensitivity form (SweepPlan::form_built), the call stays there; anything else takes the general family as without the option
   // option sens_slot: the same for the lean slot family (2^4 / 2^5 Lindblad in fp64) - the forward sweep the plain k_forward_q32, the
-  // adjoint sweep k_adjoint_q32_sens of the same instantiation (launch_sweep_lean64 / launch_sweep_lean64_sens: one chooser)
+  // adjoint sweep k_adjoint_q32_sens of the same instantiation (launch_sweep_lean64 in the forms Plain and Sens: one chooser)
   const int latch0 = h->sub_latch;
   bool lean = false;
   Family fam = Family::General;  // the family both sweeps of the call run on

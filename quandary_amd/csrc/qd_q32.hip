@@ -1655,8 +1655,9 @@ static int lean64_sb(const SweepArgs& a, const TuneOpts& o) {
   return a.nb <= 256 ? 1 : 2;
 }
 
-// What the unit's form asks of the sweep's arguments, and the name of its entry points.  Sets (parameter-set batch): a.nb states =
-// a.nb / a.nb_set sets, each reading its own control table.  Vars (model-parameter ensemble): the same axis, one control table, the
+// What the unit's form asks of the sweep's arguments, and the name of its two choosers (private to this file: the entry points
+// launch_sweep_f32 / launch_sweep_lean64 (Form, ...) of the plain unit, at the end, switch over them).
+// Sets (parameter-set batch): a.nb states = a.nb / a.nb_set sets, each reading its own control table.  Vars (model-parameter ensemble): the same axis, one control table, the
 // constants table in a.S.hcr - a dense handle or a missing table is an error.  Neither form has Krylov kernels (the degree tuner keeps
 // statistics per handle that a launch of mixed sets would blur): a request for one is an error, never another kernel.
 // Sens (model-constant sensitivities): the adjoint sweep of a single evaluation on a stationary iteration, with the stored stages and the
@@ -1764,6 +1765,32 @@ hipError_t launch_apply_lean64(const DevSys& S, const double* ctlrow, int transp
   if (S.Q == 5 && S.hasJ) return go_app<5, 1, double, true>(S, ctlrow, transpose, x, y, nb, 1, st);
   if (S.Q == 4) return go_app<4, 0, double>(S, ctlrow, transpose, x, y, nb, 1, st);
   return go_app<5, 2, double>(S, ctlrow, transpose, x, y, nb, 1, st);
+}
+
+// The sweep entry points of the two slot families (qd_internal.h): the chooser of the form's unit.  No fp32-mixed sensitivity form and no
+// pair form: an error.
+#define QD_Q32_UNIT(name) hipError_t name(const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st)
+QD_Q32_UNIT(launch_sweep_f32_sets);
+QD_Q32_UNIT(launch_sweep_f32_vars);
+QD_Q32_UNIT(launch_sweep_lean64_sets);
+QD_Q32_UNIT(launch_sweep_lean64_vars);
+QD_Q32_UNIT(launch_sweep_lean64_sens);
+hipError_t launch_sweep_f32(Form form, const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  switch (form) {
+    case Form::Plain: return launch_sweep_f32(a, adjoint, o, st);
+    case Form::Sets: return launch_sweep_f32_sets(a, adjoint, o, st);
+    case Form::Vars: return launch_sweep_f32_vars(a, adjoint, o, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_sweep_lean64(Form form, const SweepArgs& a, bool adjoint, const TuneOpts& o, hipStream_t st) {
+  switch (form) {
+    case Form::Plain: return launch_sweep_lean64(a, adjoint, o, st);
+    case Form::Sets: return launch_sweep_lean64_sets(a, adjoint, o, st);
+    case Form::Vars: return launch_sweep_lean64_vars(a, adjoint, o, st);
+    case Form::Sens: return launch_sweep_lean64_sens(a, adjoint, o, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 #endif  // !QD_SETS && !QD_VARS && !QD_SENS
 
