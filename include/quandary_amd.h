@@ -492,6 +492,43 @@ int qd_optim_evalGradF_ensemble_model(qd_optim* o, const double* alpha, int nvar
 int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_objective_value* val, double* grad, double* d_transfreq,
                              double* d_selfkerr, double* d_crosskerr);
 
+/* Sampled controls: OptimProblem::evalF / evalGradF (src/optimproblem.cpp:224-538) with p_k(t), q_k(t) given as samples in place of the
+ * spline parameters alpha - pulses from an AWG sample file, the piecewise-constant amplitudes of a GRAPE-style optimiser, the output of
+ * a filter chain or a pulse-generating model - and the gradient per sample.  Every sweep kernel reads its controls from the control
+ * table, one row per sub-step of the stepper (IMR: ntime rows, row n at t_n + dt / 2; IMR4 / IMR8: stages x ntime rows at the stage
+ * midpoints, which are not uniform); qd_sampled_nrows is the number of rows of this handle's table (QD_ERR_UNSUPPORTED for explicit
+ * Euler), qd_sampled_times copies the time t [nrows] and the signed length hstep [nrows, may be NULL] of every row, in ns.
+ * samples [nsamp][nosc][2] = (p, q) in rad/ns in the rotating frame: the layout and the unit of qd_eval_controls.  A table row at time t
+ * in (0, T), T = ntime dt, reads its (p_k, q_k) by mode:
+ *   QD_SAMPLED_ROWS    nsamp == nrows; row s reads sample s.
+ *   QD_SAMPLED_HOLD    nsamp >= 1 equal slots (the zero-order hold of an AWG); the row reads slot min(nsamp - 1, floor(t nsamp / T)).
+ *   QD_SAMPLED_LINEAR  nsamp >= 2 knots tau_j = j T / (nsamp - 1); the row reads the linear interpolant between the two neighbouring knots.
+ * The table is filled on the device (k_table_sampled) and the sweeps, the plan and the kernel families are those of the single evaluation
+ * - standard model and user Hamiltonians (qd_set_hamiltonian) alike, chunked shards included; the solver gates decide from the amplitude
+ * bound max_j max(|p_jk|, |q_jk|) of the samples, which bounds every row under all three modes (a handle that never saw qd_set_params
+ * is fine).  *val is what qd_optim_evalF returns for a control function with those table rows, except that the Tikhonov term `regul` and
+ * `penalty_variation` are defined on alpha: both are 0 here and carry no gradient.  The forward sweep of qd_optim_evalF_sampled is the
+ * one of qd_optim_evalF: it may propagate Hermitian pairs where option pair_hermitian admits them (nothing in the pairing reads alpha).
+ * grad_samples [nsamp][nosc][2] = d objective / d sample: the discrete gradient, exact to the tolerance of the linear solver like the
+ * control gradient.  The adjoint sweep leaves d objective / d p_k(t_s), d q_k(t_s) per table row; ROWS returns those sums themselves,
+ * HOLD and LINEAR the transpose of the interpolation applied to them (k_grad_sampled: one wave per entry, lanes over the rows in the
+ * support of the sample, reduced in a fixed order - two calls return the same bits; a sample with no row in its support gets exactly 0).
+ * Errors, none of which launches a sweep: a null o, samples, val or grad_samples, an unknown mode, nsamp out of range for the mode
+ * (ROWS: nsamp != nrows), a non-finite sample: QD_ERR_INVALID; an objective created with nranks > 1: QD_ERR_STATE; explicit Euler (its
+ * table has a row more, at other times), a handle with pi-pulses (they would overwrite the samples), gamma_penalty_energy > 1e-13 (that
+ * penalty reads the controls on a time grid of its own, which the samples do not define), QD_PRECISION_F32MIXED (not built for this
+ * call): QD_ERR_UNSUPPORTED, the message naming the reason.
+ * After either call the handle holds no stored trajectory and its control table is stale, as after a batch call; the solver latch,
+ * the tuner of the polynomial degree and the handle's own parameters are what they were: the next qd_optim_evalGradF(alpha) returns what
+ * it returned before, on the kernels it ran on before.
+ * Not built: explicit Euler, the energy penalty, pi-pulses, several ranks, sampled controls in the batch / ensemble / sensitivity calls,
+ * device-pointer variants, a config key of the driver. */
+enum { QD_SAMPLED_ROWS = 0, QD_SAMPLED_HOLD = 1, QD_SAMPLED_LINEAR = 2 };
+int qd_sampled_nrows(const qd_handle* h);
+int qd_sampled_times(const qd_handle* h, double* t, double* hstep);
+int qd_optim_evalF_sampled(qd_optim* o, int mode, int nsamp, const double* samples, qd_objective_value* val);
+int qd_optim_evalGradF_sampled(qd_optim* o, int mode, int nsamp, const double* samples, qd_objective_value* val, double* grad_samples);
+
 /* ---------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, initial conditions sharded over the ranks.
  * Replaces the reference's comm_init communicator (src/main.cpp:133-177) and its

@@ -183,7 +183,10 @@ EXPORTS = [
     "qd_optim_evalF_ensemble", "qd_optim_evalGradF_ensemble",
     "qd_optim_evalF_ensemble_model", "qd_optim_evalGradF_ensemble_model", "qd_optim_evalGradF_model",
     "qd_optim_last_paired", "qd_optim_last_local_results",
+    "qd_sampled_nrows", "qd_sampled_times", "qd_optim_evalF_sampled", "qd_optim_evalGradF_sampled",
 ]
+# QD_SAMPLED_*: how a control-table row reads the samples of qd_optim_evalF_sampled / qd_optim_evalGradF_sampled
+SAMPLED_MODES = {"rows": 0, "hold": 1, "linear": 2}
 COMM_ID_BYTES = 128
 PRECISION = {"f64": 0, "f32mixed": 1}
 c_u8p = C.POINTER(C.c_uint8)
@@ -263,6 +266,10 @@ def load_library(path=None):
     lib.qd_optim_evalGradF_ensemble_model.argtypes = [vp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(qd_objective_value),
                                                       C.POINTER(qd_objective_value), c_dp, c_dp]
     lib.qd_optim_evalGradF_model.argtypes = [vp, c_dp, C.POINTER(qd_objective_value), c_dp, c_dp, c_dp, c_dp]
+    lib.qd_sampled_nrows.argtypes = [vp]
+    lib.qd_sampled_times.argtypes = [vp, c_dp, c_dp]
+    lib.qd_optim_evalF_sampled.argtypes = [vp, C.c_int, C.c_int, c_dp, C.POINTER(qd_objective_value)]
+    lib.qd_optim_evalGradF_sampled.argtypes = [vp, C.c_int, C.c_int, c_dp, C.POINTER(qd_objective_value), c_dp]
     lib.qd_comm_unique_id.argtypes = [c_u8p]
     lib.qd_comm_create.argtypes = [c_u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     lib.qd_comm_create_from_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp)]
@@ -393,6 +400,16 @@ class Handle:
         pq = np.zeros((times.size, nosc, 2))
         _check(self.lib, self.lib.qd_eval_controls(self._h, dptr(times), times.size, dptr(pq)), "qd_eval_controls")
         return pq
+
+    def sampled_times(self):
+        """qd_sampled_times: (t, h) - the time and the signed step length of every row of the control table, what a sample of
+        mode 'rows' (Optim.evalF_sampled) is attached to."""
+        n = self.lib.qd_sampled_nrows(self._h)
+        if n < 0:
+            _check(self.lib, n, "qd_sampled_nrows")
+        t, h = np.zeros(n), np.zeros(n)
+        _check(self.lib, self.lib.qd_sampled_times(self._h, dptr(t), dptr(h)), "qd_sampled_times")
+        return t, h
 
     def apply_rhs(self, t, x, transpose=False):
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 2 * self.dim)
@@ -560,6 +577,30 @@ class Optim:
         g = np.zeros(max(self.h.ndesign, 1))
         _check(self.lib, self.lib.qd_optim_evalGradF(self._o, dptr(alpha), C.byref(val), dptr(g)), "qd_optim_evalGradF")
         return val.as_dict(), g[: self.h.ndesign]
+
+    def _samples(self, samples):
+        samples = np.ascontiguousarray(samples, dtype=np.float64)
+        if samples.ndim != 3 or samples.shape[1:] != (self.spec.system.nosc, 2):
+            raise ValueError(f"samples must be [nsamp, {self.spec.system.nosc}, 2] = (p, q) per oscillator, got {samples.shape}")
+        return samples
+
+    def evalF_sampled(self, samples, mode="rows"):
+        """qd_optim_evalF_sampled: the objective with p_k, q_k given as samples [nsamp, nosc, 2] (rad/ns, the layout of
+        Handle.eval_controls) read by `mode` - 'rows' (one sample per row of Handle.sampled_times), 'hold' or 'linear'."""
+        samples = self._samples(samples)
+        val = qd_objective_value()
+        _check(self.lib, self.lib.qd_optim_evalF_sampled(self._o, SAMPLED_MODES[mode], samples.shape[0], dptr(samples), C.byref(val)),
+               "qd_optim_evalF_sampled")
+        return val.as_dict()
+
+    def evalGradF_sampled(self, samples, mode="rows"):
+        """qd_optim_evalGradF_sampled: (dict, grad) with grad = d objective / d sample, shaped like samples."""
+        samples = self._samples(samples)
+        val = qd_objective_value()
+        g = np.zeros_like(samples)
+        _check(self.lib, self.lib.qd_optim_evalGradF_sampled(self._o, SAMPLED_MODES[mode], samples.shape[0], dptr(samples), C.byref(val),
+                                                             dptr(g)), "qd_optim_evalGradF_sampled")
+        return val.as_dict(), g
 
     @property
     def last_chunks(self):

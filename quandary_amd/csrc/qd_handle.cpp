@@ -71,7 +71,8 @@ extern "C" void qd_destroy(qd_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   struct Quiet { ~Quiet() { (void)hipGetLastError(); } } quiet;  // teardown never leaves a sticky error behind
-  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0, &h->d_vconst, &h->d_pencarry, &h->d_sens, &h->d_senssum}) b->release();
+  for (DBuf* b : {&h->d_bparams, &h->d_btable, &h->d_betable, &h->d_bgrad, &h->d_bgtab, &h->d_eg0, &h->d_vconst, &h->d_pencarry, &h->d_sens, &h->d_senssum, &h->d_samples, &h->d_sgrad}) b->release();
+  h->h_samples.release();
   h->h_bparams.release();
   h->h_betable.release();
   h->h_bgrad.release();
@@ -340,6 +341,23 @@ extern "C" int qd_dim_rho(const qd_handle* h) { return h ? h->S.N : QD_ERR_INVAL
 extern "C" int qd_dim_ess(const qd_handle* h) { return h ? h->dim_ess : QD_ERR_INVALID; }
 extern "C" int qd_ndesign(const qd_handle* h) { return h ? h->ndesign : QD_ERR_INVALID; }
 
+// rows of the control table and their (time, step length): what a sample of QD_SAMPLED_ROWS is attached to
+extern "C" int qd_sampled_nrows(const qd_handle* h) {
+  if (!h) return fail(QD_ERR_INVALID, "qd_sampled_nrows: null handle");
+  if (h->sol.stepper == QD_STEPPER_EE)
+    return fail(QD_ERR_UNSUPPORTED, "qd_sampled_nrows: explicit Euler - its control table has a row more, at other times; sampled controls are built for the implicit-midpoint family");
+  return (int)h->sched_t.size();
+}
+
+extern "C" int qd_sampled_times(const qd_handle* h, double* t, double* hstep) {
+  if (!h || !t) return fail(QD_ERR_INVALID, "qd_sampled_times: null argument");
+  const int n = qd_sampled_nrows(h);
+  if (n < 0) return n;
+  std::copy(h->sched_t.begin(), h->sched_t.end(), t);
+  if (hstep) std::copy(h->sched_h.begin(), h->sched_h.end(), hstep);
+  return QD_OK;
+}
+
 // largest row sum (and column sum, should a caller hand over a non-Hermitian matrix) of |a + i b|, N x N row-major: the Gershgorin bound
 // of the solver gates (row_bounds).  H is Hermitian, so the row sums bound the column sums too.
 static double rowsum_max(int N, const double* a, const double* b) {
@@ -457,8 +475,14 @@ extern "C" int qd_set_params(qd_handle* h, const double* alpha, int ndesign) {
 int qd_handle::refresh_tables() {
   if (!params_dirty) return QD_OK;
   // step table + energy-penalty table in one launch; it also resets the RHS-application counter of the sweep
-  QD_HIP(launch_controls2(dctl, d_params.p, d_sched_t.p, d_sched_h.p, (int)sched_t.size(), d_table.p, d_etimes.p, d_ezero.p,
-                          (int)etimes.size(), d_etable.p, cs, d_napply, stream));
+  // (sampled controls: the step table from the samples; the energy-penalty table, which such a call never reads, stays as it is - and
+  //  with it what the download below leaves in h_etable)
+  if (samp_mode >= 0)
+    QD_HIP(launch_table_sampled(dctl, samp_mode, samp_n, d_samples.p, dctl.Tfinal, d_sched_t.p, d_sched_h.p, (int)sched_t.size(), d_table.p, cs,
+                                d_napply, stream));
+  else
+    QD_HIP(launch_controls2(dctl, d_params.p, d_sched_t.p, d_sched_h.p, (int)sched_t.size(), d_table.p, d_etimes.p, d_ezero.p,
+                            (int)etimes.size(), d_etable.p, cs, d_napply, stream));
   napply_zeroed = d_napply != nullptr;
   if (S.dense) {  // G(t) = -i H(t) for every table row, shared by all initial conditions
     const size_t nn = (size_t)S.N * S.N;
@@ -690,6 +714,35 @@ void qd_handle::batch_end() {
   params_dirty = true;  // (the next ordinary sweep evaluates its own table again)
 }
 
+// Sampled controls: the samples [nsamp][Q][2] to the device and, per oscillator, the bound the solver gates read in place of the spline
+// coefficients' (control_amplitude_bound).  The caller has checked mode, nsamp and that every sample is finite.
+int qd_handle::sampled_begin(int mode, int nsamp, const double* samples) {
+  QD_HIP(qd::use_device(device));
+  int r;
+  const size_t n = (size_t)nsamp * 2 * S.Q;
+  if ((r = d_samples.ensure(n)) || (r = h_samples.ensure(n))) return r;
+  std::memcpy(h_samples.p, samples, sizeof(double) * n);
+  QD_HIP(hipMemcpyAsync(d_samples.p, h_samples.p, sizeof(double) * n, hipMemcpyHostToDevice, stream));
+  samp_bound.assign(S.Q, 0.0);
+  for (int j = 0; j < nsamp; j++)
+    for (int k = 0; k < S.Q; k++) {
+      const double* v = samples + ((size_t)j * S.Q + k) * 2;
+      samp_bound[k] = std::max(samp_bound[k], std::max(fabs(v[0]), fabs(v[1])));
+    }
+  samp_mode = mode;
+  samp_n = nsamp;
+  params_dirty = true;
+  traj_valid = false;
+  return QD_OK;
+}
+
+void qd_handle::sampled_end() {
+  samp_mode = -1;
+  samp_n = 0;
+  traj_valid = false;
+  params_dirty = true;  // (the next ordinary sweep evaluates its own table again)
+}
+
 // (grads null: the gradients stay in d_bgrad, for a reduction on the device - the ensemble mean)
 int qd_handle::batch_gradient(double ebar, int nsets, double* grads) {
   QD_HIP(qd::use_device(device));
@@ -842,6 +895,7 @@ size_t qd_handle::ztraj_doubles(int nb) const {
 // max over time of |p_k(t)|, |q_k(t)| from the CURRENT control parameters: sum over carriers of max |alpha^1| + max |alpha^2| (the
 // quadratic B-splines are a partition of unity, src/controlbasis.cpp:81-96); pi-pulses by their amplitude
 double qd_handle::control_amplitude_bound(int k) const {
+  if (samp_mode >= 0) return samp_bound[k];  // sampled controls: the samples bound every row (sampled_begin), the parameters say nothing
   double amp = 0.0;
   const DevOsc& o = oscs[k];
   for (int b = 0; b < o.nseg; b++) {
@@ -1568,6 +1622,15 @@ int qd_handle::gradient_launch(double ebar, double* dgrad) {
 int qd_handle::gradient_from_coeffs(double ebar, double* grad) {
   QD_HIP(qd::use_device(device));
   int r;
+  if (samp_mode >= 0) {  // sampled controls: per sample, from the same row sums (no energy term: the call refuses that penalty)
+    const size_t n = (size_t)samp_n * 2 * S.Q;
+    if ((r = d_sgrad.ensure(n)) || (r = h_samples.ensure(n))) return r;
+    QD_HIP(launch_grad_sampled(S.Q, samp_mode, samp_n, dctl.Tfinal, d_table.p, cs, nsub, d_coeffsum.p, d_sgrad.p, stream));
+    QD_HIP(hipMemcpyAsync(h_samples.p, d_sgrad.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
+    QD_HIP(hipStreamSynchronize(stream));
+    std::memcpy(grad, h_samples.p, sizeof(double) * n);
+    return QD_OK;
+  }
   if (ndesign == 0) return QD_OK;
   if ((r = d_grad.ensure(ndesign))) return r;
   if ((r = gradient_launch(ebar, d_grad.p))) return r;

@@ -44,6 +44,14 @@ inline double model_coupling(double ghz) {  // threshold of Jkl_coupling (master
 hipError_t launch_observables(const DevSys& S, const double* traj, int f32, int nb, int nstages, int stride, int nout, int nlev_total,
                               double* expected, double* population, double* expcomp, double* popcomp, hipStream_t st);
 
+// sampled controls (qd_optim_evalF_sampled; kernels in qd_kernels.hip): the control table [nrows][cs] from samples [nsamp][Q][2] read
+// by `mode` (QD_SAMPLED_*; T = ntime dt) - what launch_controls2 does from spline parameters, the energy-penalty table apart - and the
+// gradient per sample, grad [nsamp][Q][2], from the row sums coeffsum [nrows][2 Q] the adjoint sweep leaves
+hipError_t launch_table_sampled(const DevCtlDesc& d, int mode, int nsamp, const double* samples, double T, const double* times, const double* hs,
+                                int nrows, double* table, int cs, unsigned long long* zero_me, hipStream_t st);
+hipError_t launch_grad_sampled(int Q, int mode, int nsamp, double T, const double* table, int cs, int nrows, const double* coeffsum, double* grad,
+                               hipStream_t st);
+
 // growable device buffer of doubles
 struct DBuf {
   double* p = nullptr;
@@ -285,7 +293,7 @@ struct qd_handle {
   bool stores_full(int nb, const qd::DevTarget* tg) const { return !stages_only || adjoint_reads_states(nb, tg); }
   // adjoint sweep; dxbarT/djbar device pointers; coefficient sums accumulate into d_coeffsum
   int adjoint_dev(const double* dxbarT, const double* djbar, int nb, const qd::DevTarget* tg, bool accumulate);
-  // gradient from d_coeffsum (+ energy term ebar); writes host grad[ndesign]
+  // gradient from d_coeffsum (+ energy term ebar); writes host grad[ndesign] - during a sampled call grad[samp_n][Q][2], per sample
   int gradient_from_coeffs(double ebar, double* grad);
   double energy_penalty_host() const;
   // ---- parameter-set batch (qd_optim_evalF_batch / qd_optim_evalGradF_batch, qd_optim.cpp) --------------------------------------
@@ -342,6 +350,17 @@ struct qd_handle {
   // (lean column family: per state and time slice).
   bool sens = false;
   qd::DBuf d_sens, d_senssum;
+  // Sampled controls (qd_optim_evalF_sampled / qd_optim_evalGradF_sampled): while samp_mode >= 0 the handle's controls are the samples
+  // in d_samples [samp_n][Q][2], read by mode samp_mode (QD_SAMPLED_*), not the spline parameters: refresh_tables fills d_table from
+  // them (k_table_sampled), control_amplitude_bound - and through it row_bounds and every solver gate - answers with samp_bound[k] =
+  // max_j max(|p_jk|, |q_jk|) (each mode reads convex combinations of the samples, so this bounds every row), and gradient_from_coeffs
+  // writes d objective / d sample [samp_n][Q][2] (k_grad_sampled).  `params` and d_params are not touched.
+  int samp_mode = -1, samp_n = 0;
+  qd::DBuf d_samples, d_sgrad;
+  qd::HBuf h_samples;  // staging: the samples on their way up, the gradient on its way down
+  std::vector<double> samp_bound;
+  int sampled_begin(int mode, int nsamp, const double* samples);  // upload + bounds; the control table is stale from here on
+  void sampled_end();                                             // back to the spline parameters: table stale, no stored trajectory
   size_t batch_ctl_set() const { return sched_t.size() * (size_t)cs; }    // rows the step table really has x cs
   size_t batch_etable_set() const { return etimes.size() * (size_t)cs; }
   const double* batch_table() const { return d_btable.p + (size_t)batch_first * batch_ctl_set(); }

@@ -120,6 +120,16 @@ __device__ inline void eval_control_dev(const DevCtlDesc& d, const double* __res
   }
 }
 
+// what a table row holds besides its controls - step length, time, cos / sin(eta_i t) - written by the row's k == 0 thread
+__device__ inline void control_row_tail(const DevCtlDesc& d, double* __restrict__ r, double h, double t) {
+  r[0] = h;
+  r[1] = t;
+  for (int i = 0; i < d.npairs; i++) {  // MasterEq::assemble_RHS, mastereq.cpp:671-675
+    r[2 + 2 * d.Q + i] = cos(d.eta[i] * t);
+    r[2 + 2 * d.Q + d.npairs + i] = sin(d.eta[i] * t);
+  }
+}
+
 // Two row sets in one launch (step table + energy-penalty table of one parameter update); `zero_me`
 // (optional) is the RHS-application counter of the sweep that follows.  grid.y = parameter sets (launch_controls_sets): set j reads
 // params + j * ndesign and writes the tables of its own, table + j * nrows * cs and table2 + j * nrows2 * cs - the set stride is the
@@ -148,14 +158,48 @@ __global__ void k_controls(const DevCtlDesc d, const double* __restrict__ params
   double* r = table + (size_t)row * cs;
   r[2 + k] = p;
   r[2 + d.Q + k] = q;
-  if (k == 0) {
-    r[0] = hs[row];
-    r[1] = t;
-    for (int i = 0; i < d.npairs; i++) {  // MasterEq::assemble_RHS, mastereq.cpp:671-675
-      r[2 + 2 * d.Q + i] = cos(d.eta[i] * t);
-      r[2 + 2 * d.Q + d.npairs + i] = sin(d.eta[i] * t);
-    }
+  if (k == 0) control_row_tail(d, r, hs[row], t);
+}
+
+// Sampled controls (qd_optim_evalF_sampled): which samples a table row at time t reads, and how.  The row's (p_k, q_k) is
+// (1 - w1) sample[j0] + w1 sample[j0 + 1]; w1 = 0 for ROWS (j0 = the row) and HOLD (j0 = the slot of t), where sample j0 + 1 is never
+// read.  T = ntime dt.  THE definition for both directions: k_table_sampled interpolates with it, k_grad_sampled transposes it.
+__device__ inline void sampled_stencil(int mode, int nsamp, double T, int row, double t, int& j0, double& w1) {
+  w1 = 0.0;
+  if (mode == QD_SAMPLED_ROWS) {
+    j0 = row;
+  } else if (mode == QD_SAMPLED_HOLD) {
+    j0 = min(nsamp - 1, max(0, (int)floor(t * nsamp / T)));
+  } else {  // knots tau_j = j T / (nsamp - 1)
+    const double x = t * (nsamp - 1) / T;
+    j0 = min(nsamp - 2, max(0, (int)floor(x)));
+    w1 = x - j0;
   }
+}
+
+// The control table from samples [nsamp][Q][2] = (p, q) in place of k_controls: one thread per (row, oscillator), the same indexing.
+// The energy-penalty table is not written (the call refuses that penalty).
+__global__ void k_table_sampled(const DevCtlDesc d, int mode, int nsamp, const double* __restrict__ samples, double T,
+                                const double* __restrict__ times, const double* __restrict__ hs, int nrows, double* __restrict__ table,
+                                int cs, unsigned long long* __restrict__ zero_me) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx == 0 && zero_me) *zero_me = 0ull;
+  const int row = idx / d.Q, k = idx % d.Q;
+  if (row >= nrows) return;
+  const double t = times[row];
+  int j0;
+  double w1;
+  sampled_stencil(mode, nsamp, T, row, t, j0, w1);
+  const double* v = samples + ((size_t)j0 * d.Q + k) * 2;
+  double p = v[0], q = v[1];
+  if (mode == QD_SAMPLED_LINEAR) {
+    p = (1.0 - w1) * p + w1 * v[2 * d.Q];
+    q = (1.0 - w1) * q + w1 * v[2 * d.Q + 1];
+  }
+  double* r = table + (size_t)row * cs;
+  r[2 + k] = p;
+  r[2 + d.Q + k] = q;
+  if (k == 0) control_row_tail(d, r, hs[row], t);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -290,6 +334,32 @@ __global__ void __launch_bounds__(64) k_grad(const DevCtlDesc d, const double* _
       const double b1bar = si * qbar + co * pbar, b2bar = co * qbar - si * pbar;
       acc += B * (step ? g.a1 * b1bar + g.a2 * b2bar : part == 0 ? b1bar : b2bar);
     }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) grad[idx] = acc;
+}
+
+// Sampled controls: grad[j][k][part] = sum_s W[s][j] coeffsum[s][k][part], the transpose of the interpolation k_table_sampled applied
+// (sampled_stencil) - one wave per entry, lanes stride over the table rows, fixed-order wave reduction, no atomics.  Whether a row lies
+// in the support of sample j is read from the row's own time (row[1]): the stage times of the composite steppers are neither uniform nor
+// monotone, so every row is asked.  A sample no row reads gets exactly 0.  ROWS: W is the identity, the entry is the row's sum itself.
+__global__ void __launch_bounds__(64) k_grad_sampled(int Q, int mode, int nsamp, double T, const double* __restrict__ table, int cs, int nrows,
+                                                     const double* __restrict__ coeffsum, double* __restrict__ grad) {
+  const int idx = blockIdx.x, lane = threadIdx.x;
+  if (idx >= nsamp * 2 * Q) return;
+  const int j = idx / (2 * Q), kp = idx % (2 * Q);  // kp = 2 k + part: the column of coeffsum
+  if (mode == QD_SAMPLED_ROWS) {
+    if (lane == 0) grad[idx] = coeffsum[(size_t)j * 2 * Q + kp];
+    return;
+  }
+  double acc = 0.0;
+  for (int s = lane; s < nrows; s += 64) {
+    int j0;
+    double w1;
+    sampled_stencil(mode, nsamp, T, s, table[(size_t)s * cs + 1], j0, w1);
+    const bool linear = mode == QD_SAMPLED_LINEAR;
+    const double w = j == j0 ? (linear ? 1.0 - w1 : 1.0) : (linear && j == j0 + 1) ? w1 : 0.0;
+    if (w != 0.0) acc += w * coeffsum[(size_t)s * 2 * Q + kp];
   }
   acc = wave_sum(acc);
   if (lane == 0) grad[idx] = acc;
@@ -798,6 +868,22 @@ hipError_t launch_controls_sets(const DevCtlDesc& d, const double* params, int n
   if (nset < 1 || nset > 65535) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_controls, dim3((total > 0 ? total + 127 : 128) / 128, nset), dim3(128), 0, st, d, params, times, hs, nrows, table,
                      times2, hs2, nrows2, table2, cs, zero_me, ndesign);
+  return hipGetLastError();
+}
+
+// sampled controls (declared in qd_handle.h): the control table from samples, and the gradient per sample from the row sums
+hipError_t launch_table_sampled(const DevCtlDesc& d, int mode, int nsamp, const double* samples, double T, const double* times, const double* hs,
+                                int nrows, double* table, int cs, unsigned long long* zero_me, hipStream_t st) {
+  const int total = nrows * d.Q;
+  if (nsamp < 1 || (mode == QD_SAMPLED_ROWS && nsamp != nrows) || (mode == QD_SAMPLED_LINEAR && nsamp < 2) || total < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_table_sampled, dim3((total + 127) / 128), dim3(128), 0, st, d, mode, nsamp, samples, T, times, hs, nrows, table, cs, zero_me);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_sampled(int Q, int mode, int nsamp, double T, const double* table, int cs, int nrows, const double* coeffsum, double* grad,
+                               hipStream_t st) {
+  if (nsamp < 1 || (mode == QD_SAMPLED_ROWS && nsamp != nrows) || (mode == QD_SAMPLED_LINEAR && nsamp < 2)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_grad_sampled, dim3(nsamp * 2 * Q), dim3(64), 0, st, Q, mode, nsamp, T, table, cs, nrows, coeffsum, grad);
   return hipGetLastError();
 }
 

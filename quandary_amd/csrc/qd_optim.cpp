@@ -658,17 +658,19 @@ extern "C" int qd_optim_finalize(qd_optim* o, const double* alpha, const double*
   // src/optimproblem.cpp:300-329
   val->fidelity = h->S.lindblad ? s[QD_SUM_FID_RE] : s[QD_SUM_FID_RE] * s[QD_SUM_FID_RE] + s[QD_SUM_FID_IM] * s[QD_SUM_FID_IM];
   val->cost = finalize_J(o, s[QD_SUM_COST_RE], s[QD_SUM_COST_IM]);
+  // (sampled controls: the Tikhonov and control-variation terms are functions of alpha, which such a call does not have - both are 0)
+  const bool on_alpha = h->samp_mode < 0;
   double xn2 = 0.0;
-  for (int i = 0; i < h->ndesign; i++) {
+  for (int i = 0; on_alpha && i < h->ndesign; i++) {
     const double d = alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]);
     xn2 += d * d;
   }
   const double xnorm = sqrt(xn2);
-  val->regul = o->gamma_tik / 2. * xnorm * xnorm;
+  val->regul = on_alpha ? o->gamma_tik / 2. * xnorm * xnorm : 0.0;
   val->penalty = s[QD_SUM_PENALTY];
   val->penalty_dpdm = s[QD_SUM_DPDM];
   val->penalty_energy = s[QD_SUM_ENERGY];
-  val->penalty_variation = 0.5 * o->gamma_var * control_variation(h, alpha, nullptr, 0.0);
+  val->penalty_variation = on_alpha ? 0.5 * o->gamma_var * control_variation(h, alpha, nullptr, 0.0) : 0.0;
   val->objective = val->cost + val->regul + val->penalty + val->penalty_dpdm + val->penalty_energy + val->penalty_variation;
   return QD_OK;
 }
@@ -723,7 +725,7 @@ extern "C" int qd_optim_adjoint_local(qd_optim* o, const double* alpha, const do
     }
   }
   if ((r = h->gradient_from_coeffs(ebar, grad))) return r;
-  if (o->rank == 0) {  // regularisation terms on ONE rank only (src/optimproblem.cpp:356-372)
+  if (o->rank == 0 && h->samp_mode < 0) {  // regularisation terms on ONE rank only (src/optimproblem.cpp:356-372); none per sample
     for (int i = 0; i < nd; i++) grad[i] += o->gamma_tik * (alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]));
     control_variation(h, alpha, grad, 0.5 * o->gamma_var);
   }
@@ -839,6 +841,7 @@ extern "C" int qd_optim_evalGradF(qd_optim* o, const double* alpha, qd_objective
       QD_HIP(qd::use_device(o->h->device));
       if ((r = gradient_one_pass(o, alpha, sums, grad))) return r;
       if ((r = qd_optim_finalize(o, alpha, sums, val))) return r;
+      if (o->h->samp_mode >= 0) return QD_OK;  // (sampled controls: grad is per sample, the regularisation terms are not)
       const int nd = o->h->ndesign;
       for (int i = 0; i < nd; i++) grad[i] += o->gamma_tik * (alpha[i] - (o->alpha0.empty() ? 0.0 : o->alpha0[i]));
       control_variation(o->h, alpha, grad, 0.5 * o->gamma_var);
@@ -1507,4 +1510,70 @@ extern "C" int qd_optim_evalGradF_model(qd_optim* o, const double* alpha, qd_obj
   for (int p = 0; p < np; p++)
     if (d_crosskerr) d_crosskerr[p] = -2.0 * M_PI * s[2 * Q + p];
   return QD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Sampled controls: evalF / evalGradF with p_k(t), q_k(t) given as samples.  Every sweep kernel reads its controls from the control
+// table and every adjoint kernel leaves d objective / d p_k(t_s), d q_k(t_s) per table row, so the call is the single evaluation with
+// two small kernels exchanged: k_table_sampled fills the table (qd_handle::refresh_tables), k_grad_sampled reads the gradient out of the
+// row sums (qd_handle::gradient_from_coeffs).  What the host derives from the spline parameters is switched with them: the amplitude
+// bound behind every solver gate (qd_handle::control_amplitude_bound) and the regularisation terms (qd_optim_finalize and the gradient
+// paths above).  The handle's own parameters are handed through unchanged - they are what the next spline evaluation finds.
+// ---------------------------------------------------------------------------------------------------------------
+// leaves the handle on its spline parameters, its stand-in latch and its tuner state however the call ends
+struct SampledScope {
+  qd_handle* h;
+  int latch, poly[7];
+  bool frozen, params_set;
+  explicit SampledScope(qd_handle* hh)
+      : h(hh), latch(hh->sub_latch), poly{hh->poly_cur, hh->poly_lo, hh->poly_hi, hh->last_poly, hh->poly_steps, hh->fwd_poly, hh->poly_slow},
+        frozen(hh->poly_frozen), params_set(hh->params_set) {
+    h->sub_latch = -1;  // (the gates decide for the samples, as on a fresh handle)
+  }
+  ~SampledScope() {
+    h->sampled_end();
+    h->sub_latch = latch;
+    h->poly_cur = poly[0], h->poly_lo = poly[1], h->poly_hi = poly[2], h->last_poly = poly[3], h->poly_steps = poly[4], h->fwd_poly = poly[5],
+    h->poly_slow = poly[6], h->poly_frozen = frozen;
+    h->params_set = params_set;
+  }
+};
+
+static int sampled_eval(qd_optim* o, int mode, int nsamp, const double* samples, qd_objective_value* val, double* grad_samples, bool grad_mode,
+                        const std::string& who) {
+  if (!o || !samples || !val || (grad_mode && !grad_samples)) return fail(QD_ERR_INVALID, who + ": null argument");
+  if (o->nranks != 1) return fail(QD_ERR_STATE, who + ": single-rank entry point");
+  qd_handle* h = o->h;
+  if (mode != QD_SAMPLED_ROWS && mode != QD_SAMPLED_HOLD && mode != QD_SAMPLED_LINEAR)
+    return fail(QD_ERR_INVALID, who + ": unknown mode (QD_SAMPLED_ROWS, QD_SAMPLED_HOLD, QD_SAMPLED_LINEAR)");
+  if (h->sol.stepper == QD_STEPPER_EE)
+    return fail(QD_ERR_UNSUPPORTED, who + ": explicit Euler - its control table has a row more, at other times; sampled controls are built for the implicit-midpoint family");
+  if (h->has_pipulse) return fail(QD_ERR_UNSUPPORTED, who + ": the handle has pi-pulses, which would overwrite the samples");
+  if (grad_mode && h->has_ampbasis)
+    return fail(QD_ERR_UNSUPPORTED, who + ": a handle with a spline_amplitude segment has no adjoint sweep (qd_optim_evalGradF)");
+  if (o->pen.gamma_penalty_energy > 1e-13)
+    return fail(QD_ERR_UNSUPPORTED, who + ": the energy penalty (optim_penalty_energy) reads the controls on a time grid of its own, which the samples do not define");
+  if (h->precision == QD_PRECISION_F32MIXED) return fail(QD_ERR_UNSUPPORTED, who + ": fp32-mixed precision - sampled controls are not built for it");
+  const int nrows = (int)h->sched_t.size();
+  if (mode == QD_SAMPLED_ROWS ? nsamp != nrows : nsamp < (mode == QD_SAMPLED_LINEAR ? 2 : 1))
+    return fail(QD_ERR_INVALID, who + ": nsamp out of range for the mode (ROWS: qd_sampled_nrows, HOLD: >= 1, LINEAR: >= 2)");
+  if ((double)nsamp * 2.0 * h->S.Q > 2147483647.0) return fail(QD_ERR_INVALID, who + ": nsamp x nosc x 2 exceeds the 32-bit index of the gradient kernel");
+  for (size_t i = 0, n = (size_t)nsamp * 2 * h->S.Q; i < n; i++)
+    if (!std::isfinite(samples[i])) return fail(QD_ERR_INVALID, who + ": non-finite sample");
+  int r;
+  const std::vector<double> alpha = h->params;  // the handle's own parameters: handed through, never read for this call's controls
+  SampledScope scope(h);
+  if ((r = h->sampled_begin(mode, nsamp, samples))) return r;
+  r = grad_mode ? qd_optim_evalGradF(o, alpha.data(), val, grad_samples) : qd_optim_evalF(o, alpha.data(), val);
+  o->stored = false;  // (the batch calls' state: no trajectory, no pending forward sweep)
+  o->forward_done = false;
+  return r;
+}
+
+extern "C" int qd_optim_evalF_sampled(qd_optim* o, int mode, int nsamp, const double* samples, qd_objective_value* val) {
+  return sampled_eval(o, mode, nsamp, samples, val, nullptr, false, "qd_optim_evalF_sampled");
+}
+
+extern "C" int qd_optim_evalGradF_sampled(qd_optim* o, int mode, int nsamp, const double* samples, qd_objective_value* val, double* grad_samples) {
+  return sampled_eval(o, mode, nsamp, samples, val, grad_samples, true, "qd_optim_evalGradF_sampled");
 }
